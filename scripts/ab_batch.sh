@@ -5,7 +5,7 @@ R="${AB_ROUNDS:-2}"
 mkdir -p gpurun_out
 for r in $(seq "$R"); do
   for L in "$@"; do
-    v=$(LO_ICP_LIB="$L" timeout -k 10 300 python bench.py --no-cpu-baseline --pmc off --batch 1024,4096 --sequences 0 \
+    v=$(LO_ICP_LIB="$L" timeout -k 10 300 python bench.py --full --no-cpu-baseline --pmc off --batch 1024,4096 --sequences 0 \
         --steps 300 --warmup 20 | python -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])

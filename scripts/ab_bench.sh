@@ -7,7 +7,7 @@ if [ $# -eq 3 ] && [[ "$3" =~ ^[0-9]+$ ]]; then LIBS=("$1" "$2"); R="$3"; else L
 mkdir -p gpurun_out
 for r in $(seq "$R"); do
   for L in "${LIBS[@]}"; do
-    v=$(LO_ICP_LIB="$L" timeout -k 10 300 python bench.py --no-cpu-baseline --pmc off --batch "" --sequences 0 \
+    v=$(LO_ICP_LIB="$L" timeout -k 10 300 python bench.py --full --no-cpu-baseline --pmc off --batch "" --sequences 0 \
         --steps 2000 --warmup 40 | python -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])

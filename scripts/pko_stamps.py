@@ -11,9 +11,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 os.environ["LO_ICP_LIB"] = os.environ.get("LO_DIAG_LIB", os.path.join(ROOT, "lidar_odometry_amd", "liblo_icp_diag.so"))
 sys.path.insert(0, ROOT)
 from lidar_odometry_amd import IterativeClosestPointOptimizer, lib  # noqa: E402
+from tests import _data  # noqa: E402
 
 icp = IterativeClosestPointOptimizer(max_points=1 << 17)
-z = np.load(os.path.join(ROOT, "tests", "golden", "pko_inputs.npz"))
+z = _data.pko_inputs()
 names = ["prefix", "sample", "kmeans", "initvar", "EM", "JS"]
 for line in open(os.path.join(ROOT, "tests", "golden", "pko_golden.jsonl")):
     d = json.loads(line)

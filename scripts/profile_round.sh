@@ -31,6 +31,9 @@ all=(
 all+=("post:300:scripts/profile_post.sh")
 steps=()
 for spec in "${all[@]}"; do
+    # every bench step of this pass wants the secondary legs (CPU baseline and parity, per-kernel launches, rooflines,
+    # batch): they run only with --full
+    spec="${spec//python bench.py/python bench.py --full}"
     if [ $# -eq 0 ]; then steps+=("$spec"); continue; fi
     for want in "$@"; do [ "${spec%%:*}" = "$want" ] && steps+=("$spec"); done
 done

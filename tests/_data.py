@@ -6,15 +6,31 @@ product through the same surfel arrays, so the two sides see identical map conte
 from __future__ import annotations
 
 import functools
+import glob
+import os
 
 import numpy as np
 
 import oracle
 from lidar_odometry_amd import synth
 
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
 
 def pose12(T) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(T, dtype=np.float64)[:3, :].astype(np.float32).reshape(12))
+
+
+@functools.lru_cache(maxsize=None)
+def pko_inputs() -> dict:
+    """The PKO golden residual vectors, keys case_<i> (+ names): tests/golden/pko_inputs.npz and the
+    pko_inputs_case_<i>.npz files beside it (each vector beyond 60000 values has a file of its own, so that no
+    committed file passes 1 MiB; tests/golden/make_pko_golden.py writes them)."""
+    out = {}
+    for p in sorted(glob.glob(os.path.join(GOLDEN, "pko_inputs*.npz"))):
+        with np.load(p) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
 
 
 @functools.lru_cache(maxsize=None)

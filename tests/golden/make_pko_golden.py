@@ -3,7 +3,8 @@
 Runs ``oracle/_ref/pko_golden`` (the reference's own ``src/optimization/AdaptiveMEstimator.cpp``
 compiled in place from /root/reference by ``make -C oracle ref``) on seeded residual vectors and writes
 
-  tests/golden/pko_inputs.npz     residual vectors (inputs), keys case_<i>
+  tests/golden/pko_inputs.npz     residual vectors (inputs), keys case_<i>; the three longest in
+  tests/golden/pko_inputs_case_<i>.npz, one file each
   tests/golden/pko_golden.jsonl   reference outputs: alpha, GMM weights/means/variances, alpha grid, Z,
                                   std::shuffle(mt19937(42)) sample prefix and k-means seed draws
   tests/golden/pko_golden_kernels.jsonl  the same for the other pko_kernel_type values on a subset of the cases
@@ -95,9 +96,14 @@ def main():
                     out.write(json.dumps(rec) + "\n")
     os.remove(tmp)
     os.remove(inp)
+    # every committed file stays below 1 MiB: a vector beyond 60000 values gets a file of its own
+    # (tests/_data.py pko_inputs() reads them all back as one mapping)
+    big = [i for i, c in enumerate(cs) if len(c[1]) > 60000]
     np.savez_compressed(os.path.join(HERE, "pko_inputs.npz"),
                         names=np.array([c[0] for c in cs]),
-                        **{f"case_{i}": c[1] for i, c in enumerate(cs)})
+                        **{f"case_{i}": c[1] for i, c in enumerate(cs) if i not in big})
+    for i in big:
+        np.savez_compressed(os.path.join(HERE, f"pko_inputs_case_{i}.npz"), **{f"case_{i}": cs[i][1]})
     print(f"wrote {len(cs)} cases -> {outp}")
 
 

@@ -32,6 +32,25 @@ def test_spawn_two_ranks_dry_run():
     assert len(d["per_rank_s"]) == 2
 
 
+def test_dump_outputs_and_full_accepted(tmp_path):
+    """--dump-outputs DIR writes the last timed step's result as float32 / float64 .npy files, the same from run to
+    run; --steps is what was timed and the line carries ms_per_step; --full is accepted."""
+    import numpy as np
+    got = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        p = _run(["--gpus", "1", "--dry-run", "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path / name),
+                  *extra])
+        assert p.returncode == 0, p.stderr[-2000:]
+        d = json.loads(p.stdout.strip().splitlines()[-1])
+        assert d["steps"] == 7 and d["warmup"] == 2 and d["ms_per_step"] > 0
+        files = sorted(f.name for f in (tmp_path / name).iterdir())
+        assert files == ["record.npy"]
+        got.append(np.load(tmp_path / name / "record.npy"))
+        assert got[-1].dtype in (np.float32, np.float64) and got[-1].shape == (16,)
+        assert got[-1][13] == (2 + 7 - 1) % 4 + 1              # the LAST timed step's record (run_dry: k % 4 + 1)
+    np.testing.assert_array_equal(got[0], got[1])
+
+
 def test_world_size_mismatch_fails_loudly():
     p = _run(["--gpus", "2", "--dry-run"], {"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert p.returncode != 0

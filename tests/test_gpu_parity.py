@@ -93,7 +93,7 @@ def test_correspondences_edge_cases(icp):
 # ------------------------------------------------------------------------------------------- PKO
 def _golden():
     g = os.path.join(os.path.dirname(__file__), "golden")
-    z = np.load(os.path.join(g, "pko_inputs.npz"))
+    z = _data.pko_inputs()
     out = []
     with open(os.path.join(g, "pko_golden.jsonl")) as f:
         for line in f:
@@ -119,7 +119,7 @@ def test_pko_other_kernels_match_reference_golden():
     """Device PKO with pko_kernel_type tukey / welsch / gemanMcClure / pseudoHuber / cauchy / unknown (-> Cauchy)
     against the reference's own AdaptiveMEstimator.cpp outputs: alpha identical, GMM within 1e-9."""
     from lidar_odometry_amd import AdaptiveMEstimatorConfig, IterativeClosestPointOptimizer
-    z = np.load(os.path.join(os.path.dirname(__file__), "golden", "pko_inputs.npz"))
+    z = _data.pko_inputs()
     recs = [json.loads(l) for l in open(os.path.join(os.path.dirname(__file__), "golden", "pko_golden_kernels.jsonl"))]
     mism = []
     for kern in sorted({d["kernel"] for d in recs}):

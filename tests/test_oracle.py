@@ -6,12 +6,13 @@ import numpy as np
 import pytest
 
 import oracle
+from tests import _data
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
 
 def _golden():
-    z = np.load(os.path.join(GOLD, "pko_inputs.npz"))
+    z = _data.pko_inputs()
     with open(os.path.join(GOLD, "pko_golden.jsonl")) as f:
         for line in f:
             d = json.loads(line)
@@ -29,7 +30,7 @@ def test_pko_matches_reference_golden_bitwise(case):
 
 
 def _kernel_golden():
-    z = np.load(os.path.join(GOLD, "pko_inputs.npz"))
+    z = _data.pko_inputs()
     with open(os.path.join(GOLD, "pko_golden_kernels.jsonl")) as f:
         for line in f:
             d = json.loads(line)
