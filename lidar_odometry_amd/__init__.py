@@ -7,6 +7,7 @@ for gfx950 behind the C ABI in ``include/lo_icp.h`` (``liblo_icp.so``).
 from ._lib import LIB_PATH, lib, pinned_empty  # noqa: F401
 from .icp import (AdaptiveMEstimatorConfig, BatchOptimizer, BatchResult, ICPConfig,  # noqa: F401
                   IterativeClosestPointOptimizer, MapGeometry, OptimizationStats)
+from .iris import IrisLoopDetector, LoopCandidate, LoopClosureConfig  # noqa: F401
 
 __all__ = ["IterativeClosestPointOptimizer", "BatchOptimizer", "BatchResult", "ICPConfig", "AdaptiveMEstimatorConfig", "MapGeometry",
-           "OptimizationStats", "lib", "LIB_PATH"]
+           "OptimizationStats", "IrisLoopDetector", "LoopCandidate", "LoopClosureConfig", "lib", "LIB_PATH"]

@@ -48,6 +48,10 @@ EXPORTED_SYMBOLS = (
     "lo_pgo_create", "lo_pgo_destroy", "lo_pgo_add_first_keyframe", "lo_pgo_add_keyframe_with_odom",
     "lo_pgo_add_loop_and_optimize", "lo_pgo_get_optimized_pose", "lo_pgo_get_all_optimized_poses",
     "lo_pgo_has_keyframe", "lo_pgo_keyframe_count", "lo_pgo_loop_closure_count", "lo_pgo_clear",
+    # include/lo_iris.h
+    "lo_iris_config_default", "lo_iris_create", "lo_iris_destroy", "lo_iris_last_error", "lo_iris_size",
+    "lo_iris_capacity", "lo_iris_clear", "lo_iris_image", "lo_iris_encode", "lo_iris_add_keyframe",
+    "lo_iris_add_from_scan", "lo_iris_compare_all", "lo_iris_detect", "lo_iris_select_host", "lo_iris_bench_match",
 )
 
 
@@ -86,6 +90,15 @@ class LoOdomConfig(C.Structure):
 class LoOdomFrame(C.Structure):
     _fields_ = [("status", C.c_int), ("keyframe", C.c_int), ("icp_iterations", C.c_int), ("n_filtered", C.c_int),
                 ("n_corr", C.c_int), ("device_ms", C.c_double), ("map_ms", C.c_double)]
+
+
+class LoIrisConfig(C.Structure):
+    _fields_ = [("similarity_threshold", C.c_float), ("min_keyframe_gap", C.c_int), ("max_search_distance", C.c_float)]
+
+
+class LoIrisCandidate(C.Structure):
+    _fields_ = [("query_keyframe_id", C.c_int64), ("match_keyframe_id", C.c_int64), ("distance", C.c_float),
+                ("bias", C.c_int)]
 
 
 _lib = None
@@ -266,6 +279,30 @@ def lib():
     L.lo_map_patch_surfels.argtypes = [vp, vp, vp, vp, vp, C.c_size_t]
     L.lo_voxel_filter.restype = C.c_size_t
     L.lo_voxel_filter.argtypes = [fp, C.c_size_t, C.c_float, C.c_int, fp]
+    i64p = C.POINTER(C.c_int64)
+    L.lo_iris_config_default.restype = None
+    L.lo_iris_config_default.argtypes = [C.POINTER(LoIrisConfig)]
+    L.lo_iris_create.restype = vp
+    L.lo_iris_create.argtypes = [vp, C.c_size_t, C.POINTER(C.c_int)]
+    L.lo_iris_destroy.restype = None
+    L.lo_iris_destroy.argtypes = [vp]
+    L.lo_iris_last_error.restype = C.c_char_p
+    L.lo_iris_last_error.argtypes = [vp]
+    L.lo_iris_size.restype = C.c_size_t
+    L.lo_iris_size.argtypes = [vp]
+    L.lo_iris_capacity.restype = C.c_size_t
+    L.lo_iris_capacity.argtypes = [vp]
+    L.lo_iris_clear.argtypes = [vp]
+    L.lo_iris_image.argtypes = [vp, fp, C.c_size_t, u8p]
+    L.lo_iris_encode.argtypes = [vp, u8p, u8p, u8p]
+    L.lo_iris_add_keyframe.argtypes = [vp, C.c_int64, fp, vp, C.c_size_t, C.c_int]
+    L.lo_iris_add_from_scan.argtypes = [vp, C.c_int64, fp]
+    L.lo_iris_compare_all.argtypes = [vp, vp, C.c_size_t, C.c_int, fp, ip, ip, ip]
+    L.lo_iris_detect.argtypes = [vp, C.POINTER(LoIrisConfig), C.c_int64, fp, vp, C.c_size_t, C.c_int,
+                                 C.POINTER(LoIrisCandidate)]
+    L.lo_iris_select_host.restype = C.c_longlong
+    L.lo_iris_select_host.argtypes = [C.POINTER(LoIrisConfig), C.c_int64, fp, i64p, fp, fp, C.c_size_t]
+    L.lo_iris_bench_match.argtypes = [vp, C.c_int, fp]
     _lib = L
     return L
 
