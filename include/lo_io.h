@@ -33,6 +33,13 @@ int lo_kitti_pose_line(const float pose_3x4[12], char* out, size_t cap);
 /* KittiPlayer::save_trajectory_kitti_format (:530-546): one lo_kitti_pose_line per pose. 0 on success. */
 int lo_save_trajectory_kitti(const char* path, const float* poses_3x4, size_t n);
 
+/* util::save_point_cloud_ply (src/util/PointCloudUtils.cpp:146-184), byte for byte: the header lines "ply",
+ * "format binary_little_endian 1.0", "element vertex N", "property float x", "property float y", "property float z",
+ * "end_header" (each ended by one '\n'), then the 12 N bytes of the n AoS float3 points.  Parent directories are
+ * created.  n = 0 returns LO_IO_ERR_ARG and writes no file (the reference refuses an empty cloud).  0 on success,
+ * LO_IO_ERR_OPEN when the file cannot be written. */
+int lo_save_ply(const char* path, const float* xyz, size_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,9 @@ for gfx950 behind the C ABI in ``include/lo_icp.h`` (``liblo_icp.so``).
 from ._lib import LIB_PATH, lib, pinned_empty  # noqa: F401
 from .icp import (AdaptiveMEstimatorConfig, BatchOptimizer, BatchResult, ICPConfig,  # noqa: F401
                   IterativeClosestPointOptimizer, MapGeometry, OptimizationStats)
+from .gmap import GlobalMapBuilder  # noqa: F401
 from .iris import IrisLoopDetector, LoopCandidate, LoopClosureConfig  # noqa: F401
 
 __all__ = ["IterativeClosestPointOptimizer", "BatchOptimizer", "BatchResult", "ICPConfig", "AdaptiveMEstimatorConfig", "MapGeometry",
-           "OptimizationStats", "IrisLoopDetector", "LoopCandidate", "LoopClosureConfig", "lib", "LIB_PATH"]
+           "OptimizationStats", "IrisLoopDetector", "LoopCandidate", "LoopClosureConfig", "GlobalMapBuilder", "lib",
+           "LIB_PATH"]

@@ -43,7 +43,7 @@ EXPORTED_SYMBOLS = (
     "lo_odom_config_default_kitti", "lo_odom_create", "lo_odom_destroy", "lo_odom_last_error", "lo_odom_set_initial_pose",
     "lo_odom_process", "lo_odom_keyframe_count", "lo_odom_map_surfels", "lo_odom_set_exact", "lo_odom_flush",
     # include/lo_io.h
-    "lo_load_kitti_bin", "lo_load_ply", "lo_kitti_pose_line", "lo_save_trajectory_kitti",
+    "lo_load_kitti_bin", "lo_load_ply", "lo_kitti_pose_line", "lo_save_trajectory_kitti", "lo_save_ply",
     # include/lo_pgo.h
     "lo_pgo_create", "lo_pgo_destroy", "lo_pgo_add_first_keyframe", "lo_pgo_add_keyframe_with_odom",
     "lo_pgo_add_loop_and_optimize", "lo_pgo_get_optimized_pose", "lo_pgo_get_all_optimized_poses",
@@ -52,7 +52,12 @@ EXPORTED_SYMBOLS = (
     "lo_iris_config_default", "lo_iris_create", "lo_iris_destroy", "lo_iris_last_error", "lo_iris_size",
     "lo_iris_capacity", "lo_iris_clear", "lo_iris_image", "lo_iris_encode", "lo_iris_add_keyframe",
     "lo_iris_add_from_scan", "lo_iris_compare_all", "lo_iris_detect", "lo_iris_select_host", "lo_iris_bench_match",
+    # include/lo_gmap.h
+    "lo_gmap_create", "lo_gmap_destroy", "lo_gmap_last_error", "lo_gmap_clear", "lo_gmap_keyframes", "lo_gmap_points",
+    "lo_gmap_add_keyframe", "lo_gmap_add_from_scan", "lo_gmap_build", "lo_gmap_download", "lo_gmap_device_points",
+    "lo_gmap_save_ply", "lo_gmap_bench_build", "lo_gmap_stage_ms", "lo_gmap_voxelgrid_host",
 )
+LO_GMAP_STAGES = 4
 
 
 class LoConfig(C.Structure):
@@ -303,6 +308,31 @@ def lib():
     L.lo_iris_select_host.restype = C.c_longlong
     L.lo_iris_select_host.argtypes = [C.POINTER(LoIrisConfig), C.c_int64, fp, i64p, fp, fp, C.c_size_t]
     L.lo_iris_bench_match.argtypes = [vp, C.c_int, fp]
+    L.lo_save_ply.restype = C.c_int
+    L.lo_save_ply.argtypes = [C.c_char_p, fp, C.c_size_t]
+    szp = C.POINTER(C.c_size_t)
+    L.lo_gmap_create.restype = vp
+    L.lo_gmap_create.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_int)]
+    L.lo_gmap_destroy.restype = None
+    L.lo_gmap_destroy.argtypes = [vp]
+    L.lo_gmap_last_error.restype = C.c_char_p
+    L.lo_gmap_last_error.argtypes = [vp]
+    L.lo_gmap_clear.argtypes = [vp]
+    L.lo_gmap_keyframes.restype = C.c_size_t
+    L.lo_gmap_keyframes.argtypes = [vp]
+    L.lo_gmap_points.restype = C.c_size_t
+    L.lo_gmap_points.argtypes = [vp]
+    L.lo_gmap_add_keyframe.argtypes = [vp, C.c_int64, vp, C.c_size_t, C.c_int]
+    L.lo_gmap_add_from_scan.argtypes = [vp, C.c_int64]
+    L.lo_gmap_build.argtypes = [vp, fp, C.c_size_t, C.c_float, szp]
+    L.lo_gmap_download.restype = C.c_longlong
+    L.lo_gmap_download.argtypes = [vp, fp, C.c_size_t]
+    L.lo_gmap_device_points.argtypes = [vp, C.POINTER(vp), szp]
+    L.lo_gmap_save_ply.argtypes = [vp, C.c_char_p]
+    L.lo_gmap_bench_build.argtypes = [vp, fp, C.c_size_t, C.c_float, C.c_int, fp]
+    L.lo_gmap_stage_ms.argtypes = [vp, fp]
+    L.lo_gmap_voxelgrid_host.restype = C.c_longlong
+    L.lo_gmap_voxelgrid_host.argtypes = [fp, C.c_size_t, C.c_float, fp, C.c_size_t]
     _lib = L
     return L
 

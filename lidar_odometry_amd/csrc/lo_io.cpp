@@ -2,12 +2,14 @@
 //   * KITTI velodyne .bin (util::load_kitti_binary, src/util/PointCloudUtils.cpp:18-65);
 //   * PLY point clouds (PLYPlayer::load_ply_point_cloud / parse_ply_header, app/player/ply_player.cpp:267-461);
 //   * KITTI trajectory lines with the LiDAR -> camera frame change (KittiPlayer::pose_to_kitti_string,
-//     app/player/kitti_player.cpp:934-953; save_trajectory_kitti_format :530-546).
+//     app/player/kitti_player.cpp:934-953; save_trajectory_kitti_format :530-546);
+//   * the map's binary PLY (util::save_point_cloud_ply, src/util/PointCloudUtils.cpp:146-184).
 // Parsing follows the reference's stream semantics, including its quirks (noted inline), so a file loads to
 // the same points here as there.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <filesystem>
 #include <fstream>
 #include <sstream>
 #include <string>
@@ -194,6 +196,29 @@ int lo_save_trajectory_kitti(const char* path, const float* poses_3x4, size_t n)
         if (lo_kitti_pose_line(poses_3x4 + 12 * i, line, sizeof(line)) < 0) return LO_IO_ERR_ARG;
         f << line << '\n';
     }
+    return f.good() ? 0 : LO_IO_ERR_OPEN;
+}
+
+// save_point_cloud_ply: an empty cloud is refused before anything touches the disk; the parent directories are
+// created; the points follow the header as they lie in memory (x, y, z floats of each point in turn).
+int lo_save_ply(const char* path, const float* xyz, size_t n) {
+    if (!path || !xyz || n == 0) return LO_IO_ERR_ARG;
+    const std::filesystem::path parent = std::filesystem::path(path).parent_path();
+    if (!parent.empty()) {
+        std::error_code ec;
+        std::filesystem::create_directories(parent, ec);       // a failure shows as the open below failing
+    }
+    std::ofstream f(path, std::ios::binary);
+    if (!f.is_open()) return LO_IO_ERR_OPEN;
+    f << "ply\n";
+    f << "format binary_little_endian 1.0\n";
+    f << "element vertex " << n << "\n";
+    f << "property float x\n";
+    f << "property float y\n";
+    f << "property float z\n";
+    f << "end_header\n";
+    f.write(reinterpret_cast<const char*>(xyz), static_cast<std::streamsize>(n * 3 * sizeof(float)));
+    f.close();
     return f.good() ? 0 : LO_IO_ERR_OPEN;
 }
 
