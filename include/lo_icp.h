@@ -341,6 +341,9 @@ int lo_seq_sum_f32(lo_ctx* ctx, const float* x, size_t n, float* out_sum, long l
 int lo_debug_counters(lo_ctx* ctx, unsigned long long out[16]);
 /* Diagnostic: the first n (<= 24) device counters. */
 int lo_debug_counters_ex(lo_ctx* ctx, unsigned long long* out, int n);
+/* Diagnostic: bytes of device and pinned memory the library's handles (contexts, batches, device maps, loop detectors,
+ * map builders) hold right now, process-wide.  Back at its earlier value once the handles made since are destroyed. */
+long long lo_debug_live_bytes(void);
 /* Context-free host variant (no GPU needed): sample_size = gmm_sample_size. */
 int lo_pko_sample_indices_host(size_t n, int sample_size, int32_t* out);
 

@@ -1,0 +1,334 @@
+// lo_batch.hip — scan-parallel batch (one GPU): the lo_batch* entry points.
+//
+// B contexts advance through optimize() in lockstep: one launch per kernel per GN iteration for all jobs
+// (blockIdx.y = job).  The per-job KParams live in device memory (the batched kernels read them with scalar
+// loads); they are rebuilt on the host every call but uploaded only when a job's scan pointer, size or map
+// table changed.  The initial poses travel in a separate 12-float-per-job array (KParams::T0p).
+#include "lo_ctx_def.h"
+
+static constexpr int kBatchPkoWGs = 256;    // PKO workgroups per launch over all jobs (>= 1 per job; measured best)
+// one single-wave PKO workgroup per job (k_pko_tb<1, true>) is opt-in (LO_BATCH_ONE_WAVE=1): with the JS phase's
+// LDS alpha table the four-wave split wins at every measured size (2048 jobs 946k vs 828k scans/s, 4096 1.039M vs
+// 1.021M); the one-wave variant stays tested (tests/test_gpu_batch.py) for batches beyond the measured range
+static constexpr int kBatchOneWaveMin = 0x7fffffff;
+// from this many small jobs the accumulate and the solve are two launches (k_accumulate_b1<false> + k_solve_b1):
+// the fused form's fp64 solve holds the 8-wave accumulate at 128 VGPRs (2 workgroups per CU; split: 70, 3 per CU).
+// Measured: 4096 jobs 1.037M -> 1.090M scans/s, 1024 857k -> 875k; at 64-256 jobs the extra launch costs ~1 %.
+static constexpr int kBatchSplitSolveMin = 1024;
+
+struct lo_batch {
+    std::vector<lo_ctx*> ctx;
+    int device = 0;
+    int max_iters = 0;
+    int pko_max = 1;                 // min over contexts of the single-scan PKO grid
+    int pko_budget = kBatchPkoWGs;   // PKO workgroups per launch over all jobs (LO_BATCH_PKO_WGS overrides)
+    int one_wave_min = kBatchOneWaveMin;   // jobs from which PKO runs one wave per job (LO_BATCH_ONE_WAVE=0/1 forces)
+    int split_solve_min = kBatchSplitSolveMin;   // jobs from which k_solve_b1 solves (LO_BATCH_FUSED_SOLVE=0/1 forces)
+    hipStream_t stream = nullptr;
+    std::string err;
+    DevBuf<KParams> d_P;
+    PinnedBuf<KParams> h_P;          // staging of the active jobs' params
+    DevBuf<float> d_T0;
+    PinnedBuf<float> h_T0;
+    DevBuf<lo_batch_rec> d_rec;
+    PinnedBuf<lo_batch_rec> h_rec;
+    std::vector<float> T_in;         // count x 12 (T_out of failed / skipped jobs)
+    std::vector<int> act;            // active job -> job index
+    std::vector<size_t> n;
+    struct Sig {
+        const lo_ctx* ctx; uint64_t gen; const float* pts; int n; const Slot* tab; uint32_t log2cap; int exact;
+        // field by field: the padding after n is not initialised, so a byte compare could report a change every call
+        bool operator==(const Sig& o) const {
+            return ctx == o.ctx && gen == o.gen && pts == o.pts && n == o.n && tab == o.tab && log2cap == o.log2cap &&
+                   exact == o.exact;
+        }
+    };
+    std::vector<Sig> sig;            // what d_P currently holds, per active slot
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipEvent_t ev_go = nullptr;      // reference-exact jobs: the batch's uploads done (their streams wait on it)
+    std::vector<hipEvent_t> ev_ex;   //   and each exact job's scan finished (the batch stream waits on them)
+    int nlock = 0;                   // jobs of the last call that ran in lockstep (the first nlock params)
+    bool pending = false;
+};
+
+static int batch_alloc(lo_batch* b) {
+    const size_t B = b->ctx.size();
+    LO_HIP(b, hipSetDevice(b->device));
+    LO_HIP(b, hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+    LO_HIP(b, b->d_P.reserve(B));
+    LO_HIP(b, b->h_P.reserve(B));
+    LO_HIP(b, b->d_T0.reserve(B * 12));
+    LO_HIP(b, b->h_T0.reserve(B * 12));
+    LO_HIP(b, b->d_rec.reserve(B));
+    LO_HIP(b, b->h_rec.reserve(B));
+    LO_HIP(b, hipEventCreate(&b->ev0));
+    LO_HIP(b, hipEventCreate(&b->ev1));
+    LO_HIP(b, hipEventCreateWithFlags(&b->ev_go, hipEventDisableTiming));
+    LO_HIP(b, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pko_tb<4, false>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kMaxBlocks * sizeof(int))));
+    LO_HIP(b, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pko_tb<1, true>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kMaxBlocks * sizeof(int))));
+    LO_HIP(b, hipFuncSetAttribute(reinterpret_cast<const void*>(k_exact_acc_b), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  static_cast<int>(kXcLdsBytes)));
+    // reference-exact jobs' iteration-0 scale (k_exact_scale_cb, up to 80 KB of dynamic LDS): a process that only
+    // batches must not depend on a single-context exact optimize having set the attribute first
+    LO_HIP(b, exact_scale_c_prepare());
+    b->T_in.assign(B * 12, 0.0f);
+    b->n.assign(B, 0);
+    return LO_OK;
+}
+
+extern "C" {
+
+lo_batch* lo_batch_create(lo_ctx* const* ctxs, int count, int* err) {
+    auto fail = [&](int rc, const char* msg) -> lo_batch* {
+        std::fprintf(stderr, "lo_batch_create: %s\n", msg);
+        if (err) *err = rc;
+        return nullptr;
+    };
+    if (!ctxs || count < 1 || count > 65535) return fail(LO_ERR_ARG, "need 1..65535 contexts");
+    for (int j = 0; j < count; ++j) {
+        const lo_ctx* c = ctxs[j];
+        if (!c) return fail(LO_ERR_ARG, "null context");
+        if (c->kd) return fail(LO_ERR_ARG, "batched optimize needs surfel-mode contexts");
+        if (c->device != ctxs[0]->device) return fail(LO_ERR_ARG, "contexts on different devices");
+        if (c->cfg.max_iterations != ctxs[0]->cfg.max_iterations) return fail(LO_ERR_ARG, "max_iterations differ");
+        for (int k = 0; k < j; ++k) if (ctxs[k] == c) return fail(LO_ERR_ARG, "a context appears twice");
+    }
+    lo_batch* b = new lo_batch();
+    b->ctx.assign(ctxs, ctxs + count);
+    b->device = ctxs[0]->device;
+    b->max_iters = ctxs[0]->cfg.max_iterations;
+    b->pko_max = kPkoMaxWGs;
+    for (const lo_ctx* c : b->ctx) b->pko_max = std::min(b->pko_max, pko_grid(c->cfg));
+    if (const char* e = std::getenv("LO_BATCH_PKO_WGS")) b->pko_budget = std::max(1, std::atoi(e));
+    if (const char* e = std::getenv("LO_BATCH_ONE_WAVE")) b->one_wave_min = std::atoi(e) ? 1 : 0x7fffffff;
+    if (const char* e = std::getenv("LO_BATCH_FUSED_SOLVE")) b->split_solve_min = std::atoi(e) ? 0x7fffffff : 1;
+    const int rc = batch_alloc(b);
+    if (rc != LO_OK) {
+        std::fprintf(stderr, "lo_batch_create: %s\n", b->err.c_str());
+        lo_batch_destroy(b);
+        if (err) *err = rc;
+        return nullptr;
+    }
+    if (err) *err = LO_OK;
+    return b;
+}
+
+void lo_batch_destroy(lo_batch* b) {
+    if (!b) return;
+    (void)hipSetDevice(b->device);
+    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    if (b->ev0) (void)hipEventDestroy(b->ev0);
+    if (b->ev1) (void)hipEventDestroy(b->ev1);
+    if (b->ev_go) (void)hipEventDestroy(b->ev_go);
+    for (hipEvent_t e : b->ev_ex) (void)hipEventDestroy(e);
+    if (b->stream) (void)hipStreamDestroy(b->stream);
+    delete b;
+}
+
+const char* lo_batch_last_error(const lo_batch* b) { return b ? b->err.c_str() : "null batch"; }
+int lo_batch_size(const lo_batch* b) { return b ? static_cast<int>(b->ctx.size()) : 0; }
+
+int lo_batch_optimize_async(lo_batch* b, const float* const* d_pts, const size_t* n, const float* T_init) {
+    if (!b || !n || !T_init) return LO_ERR_ARG;
+    if (b->pending) { b->err = "batch in flight: call lo_batch_result first"; return LO_ERR_STATE; }
+    const int B = static_cast<int>(b->ctx.size());
+    for (int j = 0; j < B; ++j) {
+        if (n[j] > static_cast<size_t>(b->ctx[j]->cfg.max_points)) { b->err = "n exceeds max_points"; return LO_ERR_CAPACITY; }
+        if (b->ctx[j]->cfg.max_iterations != b->max_iters) {   // lo_update_config after lo_batch_create
+            b->err = "a context's max_iterations no longer matches the batch's";
+            return LO_ERR_STATE;
+        }
+    }
+    LO_HIP(b, hipSetDevice(b->device));
+    for (int j = 0; j < B; ++j) {                      // PKO / candidate buffers first (their pointers go into the params)
+        if (n[j] == 0) continue;
+        const int rc = ensure_acc_part(b->ctx[j]);
+        if (rc != LO_OK) { b->err = b->ctx[j]->err; return rc; }
+    }
+    std::memcpy(b->T_in.data(), T_init, sizeof(float) * 12 * B);
+    b->act.clear();
+    int max_nb = 1, max_acc = 1, n_max_ex = 1;
+    bool same = true;
+    // job order in the device params: the fast-mode jobs, then the reference-exact ones (both in lockstep), then the
+    // exact jobs too large for the one-workgroup scale (kExactMergeMax): those run their context's own exact GN loop
+    std::vector<int> fast, exl, ex;
+    for (int j = 0; j < B; ++j) {
+        b->n[j] = n[j];
+        if (n[j] == 0) continue;
+        lo_ctx* c = b->ctx[j];
+        if (!c->exact) fast.push_back(j);
+        else if (n[j] <= static_cast<size_t>(kExactMergeMax)) exl.push_back(j);
+        else ex.push_back(j);
+    }
+    const int nfast = static_cast<int>(fast.size()), nexl = static_cast<int>(exl.size());
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int j : pass ? exl : fast) {
+            lo_ctx* c = b->ctx[j];
+            const float* pts = (d_pts && d_pts[j]) ? d_pts[j] : c->d_pts;
+            const int a = static_cast<int>(b->act.size());
+            KParams P = make_params(c, pts, static_cast<int>(n[j]));
+            P.T0p = b->d_T0 + 12 * a;
+            if (pass) {                                       // the scale comes from k_exact_scale_cb (iteration 0)
+                P.scale_given = 1;
+                n_max_ex = std::max(n_max_ex, P.n);
+            } else {
+                max_acc = std::max(max_acc, P.nb_acc);
+            }
+            max_nb = std::max(max_nb, P.nb);
+            const lo_batch::Sig sg{c, c->cfg_gen, pts, P.n, P.tab, P.log2cap, pass};
+            if (a >= static_cast<int>(b->sig.size()) || !(b->sig[a] == sg)) same = false;
+            if (!same) {
+                if (a < static_cast<int>(b->sig.size())) b->sig[a] = sg; else b->sig.push_back(sg);
+            }
+            b->h_P[a] = P;
+            std::memcpy(b->h_T0 + 12 * a, T_init + 12 * j, sizeof(float) * 12);
+            b->act.push_back(j);
+        }
+    }
+    const int nact = static_cast<int>(b->act.size());
+    b->nlock = nact;
+    // large exact jobs after the lockstep ones: only their DevState pointer is read (k_export_batch)
+    for (int j : ex) {
+        b->h_P[b->act.size()] = make_params(b->ctx[j], b->ctx[j]->d_pts, static_cast<int>(n[j]));
+        b->act.push_back(j);
+    }
+    const int ntot = static_cast<int>(b->act.size());
+    if (!ex.empty()) same = false;
+    if (static_cast<int>(b->sig.size()) != ntot) { same = false; b->sig.resize(ntot); }
+    LO_HIP(b, hipEventRecord(b->ev0, b->stream));
+    if (ntot > 0) {
+        if (nact > 0) LO_HIP(b, hipMemcpyAsync(b->d_T0, b->h_T0, sizeof(float) * 12 * nact, hipMemcpyHostToDevice, b->stream));
+        if (!same) LO_HIP(b, hipMemcpyAsync(b->d_P, b->h_P, sizeof(KParams) * ntot, hipMemcpyHostToDevice, b->stream));
+    }
+    if (!ex.empty()) {
+        // large reference-exact jobs run their context's own exact GN loop (the chip-wide sequential-sum
+        // reproductions) on the context stream, ordered after the batch's uploads (lo_batch_optimize copies their
+        // points on the batch stream) and before its record export; the scan pipeline stays off for them, so every
+        // launch is on the context stream and the record is final when it ends
+        LO_HIP(b, hipEventRecord(b->ev_go, b->stream));
+        while (b->ev_ex.size() < ex.size()) {
+            hipEvent_t e = nullptr;
+            LO_HIP(b, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            b->ev_ex.push_back(e);
+        }
+        for (size_t q = 0; q < ex.size(); ++q) {
+            const int j = ex[q];
+            lo_ctx* c = b->ctx[j];
+            const float* pts = (d_pts && d_pts[j]) ? d_pts[j] : c->d_pts;
+            LO_HIP(b, hipStreamWaitEvent(c->stream, b->ev_go, 0));
+            const bool pipe = c->pipe, sync_call = c->sync_call;
+            c->pipe = false;
+            c->sync_call = false;
+            const int rc = enqueue_optimize(c, pts, n[j], T_init + 12 * j);
+            c->pipe = pipe;
+            c->sync_call = sync_call;
+            c->pending = false;                               // the batch collects the record, not lo_icp_result
+            if (rc != LO_OK) { b->err = std::string("exact job: ") + c->err; return rc; }
+            LO_HIP(b, hipEventRecord(b->ev_ex[q], c->stream));
+            LO_HIP(b, hipStreamWaitEvent(b->stream, b->ev_ex[q], 0));
+        }
+    }
+    if (nact > 0) {
+        const int pko_wgs = std::max(1, std::min(b->pko_max, b->pko_budget / nact));
+        const size_t pre_bytes = static_cast<size_t>(max_nb) * sizeof(int);
+        const dim3 blk(kBlock);
+        for (int it = 0; it < b->max_iters; ++it) {
+            hipLaunchKernelGGL(k_correspond_b, dim3(max_nb, nact), blk, 0, b->stream, b->d_P, it == 0 ? 1 : 0, it == 0 ? 1 : 0);
+            if (it == 0 && nexl > 0) {
+                launch_exact_scale_cb(b->d_P + nfast, nexl, n_max_ex, b->stream);
+                LO_HIP(b, hipGetLastError());                 // e.g. a dynamic-LDS launch the attribute did not allow
+            }
+            if (nact >= b->one_wave_min)
+                hipLaunchKernelGGL((k_pko_tb<1, true>), dim3(1, nact), dim3(64), pre_bytes, b->stream, b->d_P, it);
+            else
+                hipLaunchKernelGGL((k_pko_tb<4, false>), dim3(pko_wgs, nact), dim3(256), pre_bytes, b->stream, b->d_P, it);
+            if (nexl > 0)
+                hipLaunchKernelGGL(k_exact_acc_b, dim3(nexl), dim3(256), kXcLdsBytes, b->stream, b->d_P + nfast, it);
+            if (nfast == 0) continue;
+            if (max_acc <= kFuseMaxBlocks) {           // small jobs: one 8-wave workgroup accumulates + solves
+                if (nfast < b->split_solve_min) {
+                    hipLaunchKernelGGL(k_accumulate_b1<true>, dim3(1, nfast), dim3(512), 0, b->stream, b->d_P, it);
+                } else {
+                    hipLaunchKernelGGL(k_accumulate_b1<false>, dim3(1, nfast), dim3(512), 0, b->stream, b->d_P, it);
+                    hipLaunchKernelGGL(k_solve_b1, dim3(nfast), dim3(kBlock), 0, b->stream, b->d_P, it);
+                }
+            } else {
+                hipLaunchKernelGGL(k_accumulate_b, dim3(max_acc, nfast), blk, 0, b->stream, b->d_P, it);
+                hipLaunchKernelGGL(k_solve_b, dim3(nfast), dim3(kSolveThreads), 0, b->stream, b->d_P, it);
+            }
+        }
+    }
+    if (ntot > 0) {
+        hipLaunchKernelGGL(k_export_batch, dim3(ntot), dim3(64), 0, b->stream, b->d_P, b->d_rec);
+        LO_HIP(b, hipGetLastError());
+        LO_HIP(b, hipMemcpyAsync(b->h_rec, b->d_rec, sizeof(lo_batch_rec) * ntot, hipMemcpyDeviceToHost, b->stream));
+    }
+    LO_HIP(b, hipEventRecord(b->ev1, b->stream));
+    b->pending = true;
+    return LO_OK;
+}
+
+int lo_batch_result(lo_batch* b, lo_batch_rec* out, double* gpu_ms) {
+    if (!b || !out) return LO_ERR_ARG;
+    if (!b->pending) { b->err = "no batch in flight"; return LO_ERR_STATE; }
+    LO_HIP(b, hipSetDevice(b->device));
+    LO_HIP(b, hipStreamSynchronize(b->stream));
+    b->pending = false;
+    const int B = static_cast<int>(b->ctx.size());
+    for (int j = 0; j < B; ++j) {          // skipped jobs: the reference's false on an empty cloud (:593-603)
+        lo_batch_rec& R = out[j];
+        std::memset(&R, 0, sizeof(R));
+        R.status = LO_INSUFFICIENT;
+    }
+    for (size_t a = 0; a < b->act.size(); ++a) out[b->act[a]] = b->h_rec[a];
+    for (int j = 0; j < B; ++j)            // optimized_transform = initial unless the GN loop succeeded (:266, :301)
+        if (out[j].status != LO_OK) std::memcpy(out[j].pose, b->T_in.data() + 12 * j, sizeof(float) * 12);
+    if (gpu_ms) {
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, b->ev0, b->ev1) != hipSuccess) ms = -1.0f;
+        *gpu_ms = ms;
+    }
+    return LO_OK;
+}
+
+int lo_batch_bench_correspond(lo_batch* b, int reps, float* avg_ms) {
+    if (!b || reps < 1 || !avg_ms) return LO_ERR_ARG;
+    if (b->pending) { b->err = "batch in flight: call lo_batch_result first"; return LO_ERR_STATE; }
+    const int nact = b->nlock;
+    if (nact == 0) { b->err = "no lockstep batch has run yet"; return LO_ERR_STATE; }
+    LO_HIP(b, hipSetDevice(b->device));
+    int max_nb = 1;
+    for (int a = 0; a < nact; ++a) max_nb = std::max(max_nb, b->h_P[a].nb);
+    const dim3 grid(max_nb, nact), blk(kBlock);
+    // every job back at its initial pose with a fresh GN state (init launch), then reps plain launches
+    hipLaunchKernelGGL(k_correspond_b, grid, blk, 0, b->stream, b->d_P, 1, 1);
+    LO_HIP(b, hipEventRecord(b->ev0, b->stream));
+    for (int r = 0; r < reps; ++r) hipLaunchKernelGGL(k_correspond_b, grid, blk, 0, b->stream, b->d_P, 0, 0);
+    LO_HIP(b, hipEventRecord(b->ev1, b->stream));
+    LO_HIP(b, hipGetLastError());
+    LO_HIP(b, hipEventSynchronize(b->ev1));
+    float ms = 0.0f;
+    LO_HIP(b, hipEventElapsedTime(&ms, b->ev0, b->ev1));
+    *avg_ms = ms / reps;
+    return LO_OK;
+}
+
+int lo_batch_optimize(lo_batch* b, const float* const* pts, const size_t* n, const float* T_init, lo_batch_rec* out) {
+    if (!b || !pts || !n || !T_init || !out) return LO_ERR_ARG;
+    if (b->pending) { b->err = "batch in flight: call lo_batch_result first"; return LO_ERR_STATE; }
+    const int B = static_cast<int>(b->ctx.size());
+    LO_HIP(b, hipSetDevice(b->device));
+    for (int j = 0; j < B; ++j) {
+        if (n[j] == 0) continue;
+        if (!pts[j]) return LO_ERR_ARG;
+        if (n[j] > static_cast<size_t>(b->ctx[j]->cfg.max_points)) { b->err = "n exceeds max_points"; return LO_ERR_CAPACITY; }
+        LO_HIP(b, hipMemcpyAsync(b->ctx[j]->d_pts, pts[j], n[j] * 3 * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    }
+    const int rc = lo_batch_optimize_async(b, nullptr, n, T_init);
+    if (rc != LO_OK) return rc;
+    return lo_batch_result(b, out, nullptr);
+}
+
+}  // extern "C"

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "../../include/lo_map.h"
+#include "lo_buf.h"
 #include "lo_ctx_internal.h"
 #include "lo_device.h"
 #include "lo_math.h"
@@ -1248,7 +1249,7 @@ struct lo_devmap {
     int device = 0;
     hipStream_t stream = nullptr;
     DM M{};
-    std::vector<void*> bufs;
+    std::vector<DevBuf<void>> bufs;      // every device array of M and the scratch below (dm_alloc)
     float* d_in = nullptr;               // world points (host input / device transform target)
     float* at_c = nullptr;               // ApplyTransformAndRehash scratch: moved centroids, new keys, merged L0
     uint64_t* at_k = nullptr;
@@ -1262,32 +1263,27 @@ struct lo_devmap {
     const float* g_scan = nullptr;
     const int* g_scan_n = nullptr;
     std::string err;
-    int* h_cnt = nullptr;                // pinned copy of the counters
-    int* h_err = nullptr;                // pinned copy of the counters for lo_devmap_status_async / _poll
+    PinnedBuf<int> h_cnt;                // copy of the counters
+    PinnedBuf<int> h_err;                // copy of the counters for lo_devmap_status_async / _poll
     hipEvent_t ev_err = nullptr;         //   recorded after that copy
     bool err_pending = false;
     size_t updates = 0;
 };
 
-#define DM_HIP(m, x)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (x);                                                                  \
-        if (e_ != hipSuccess) { (m)->err = std::string(#x) + ": " + hipGetErrorString(e_); return LO_ERR_HIP; } \
-    } while (0)
-
 template <class T>
 static int dm_alloc(lo_devmap* m, T** p, size_t count, int fill_byte) {
-    void* v = nullptr;
-    DM_HIP(m, hipMalloc(&v, std::max<size_t>(count, 1) * sizeof(T)));
-    m->bufs.push_back(v);
-    DM_HIP(m, hipMemset(v, fill_byte, std::max<size_t>(count, 1) * sizeof(T)));
-    *p = static_cast<T*>(v);
+    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+    m->bufs.emplace_back();
+    DevBuf<void>& v = m->bufs.back();
+    LO_HIP(m, v.reserve(bytes));
+    LO_HIP(m, hipMemset(v, fill_byte, bytes));
+    *p = static_cast<T*>(v.get());
     return LO_OK;
 }
 
 static int dm_fill_int(lo_devmap* m, int* p, size_t count, int value) {
     std::vector<int> h(count, value);
-    DM_HIP(m, hipMemcpy(p, h.data(), count * sizeof(int), hipMemcpyHostToDevice));
+    LO_HIP(m, hipMemcpy(p, h.data(), count * sizeof(int), hipMemcpyHostToDevice));
     return LO_OK;
 }
 
@@ -1308,7 +1304,7 @@ static int dm_bind_table(lo_devmap* m) {
         hipLaunchKernelGGL(k_dm_flag, dim3(1), dim3(64), 0, m->stream, m->M, static_cast<int>(R_TAB));
         hipLaunchKernelGGL(k_dm_rebuild_clear, dim3(1024), dim3(kPar), 0, m->stream, m->M);
         hipLaunchKernelGGL(k_dm_rebuild_fill, dim3(1024), dim3(kPar), 0, m->stream, m->M);
-        DM_HIP(m, hipGetLastError());
+        LO_HIP(m, hipGetLastError());
     }
     return LO_OK;
 }
@@ -1375,8 +1371,8 @@ lo_devmap* lo_devmap_create(lo_ctx* ctx, float voxel_size, int hierarchy_factor,
     if (rc == LO_OK) rc = dm_fill_int(m, M.tpfirst, HT, INT_MAX);
     if (rc == LO_OK) rc = dm_fill_int(m, M.ttfirst, HP, INT_MAX);
     if (rc == LO_OK) rc = dm_fill_int(m, M.tqfirst, HP, INT_MAX);
-    if (rc == LO_OK && hipHostMalloc(&m->h_cnt, 16 * sizeof(int), hipHostMallocDefault) != hipSuccess) rc = LO_ERR_HIP;
-    if (rc == LO_OK && hipHostMalloc(&m->h_err, 16 * sizeof(int), hipHostMallocDefault) != hipSuccess) rc = LO_ERR_HIP;
+    if (rc == LO_OK && m->h_cnt.reserve(16) != hipSuccess) rc = LO_ERR_HIP;
+    if (rc == LO_OK && m->h_err.reserve(16) != hipSuccess) rc = LO_ERR_HIP;
     if (rc == LO_OK && hipEventCreateWithFlags(&m->ev_err, hipEventDisableTiming) != hipSuccess) rc = LO_ERR_HIP;
     if (rc == LO_OK) rc = dm_bind_table(m);
     if (rc == LO_OK && hipStreamSynchronize(m->stream) != hipSuccess) rc = LO_ERR_HIP;
@@ -1397,9 +1393,6 @@ void lo_devmap_destroy(lo_devmap* m) {
         }
     }
     if (m->gexec) (void)hipGraphExecDestroy(m->gexec);
-    for (void* p : m->bufs) (void)hipFree(p);
-    if (m->h_cnt) (void)hipHostFree(m->h_cnt);
-    if (m->h_err) (void)hipHostFree(m->h_err);
     if (m->ev_err) (void)hipEventDestroy(m->ev_err);
     delete m;
 }
@@ -1412,7 +1405,7 @@ static int dm_capture(lo_devmap* m, const int* d_scan_n, const float* d_scan) {
     DM& M = m->M;
     if (m->gexec) { (void)hipGraphExecDestroy(m->gexec); m->gexec = nullptr; }
     hipGraph_t g = nullptr;
-    DM_HIP(m, hipStreamBeginCapture(m->stream, hipStreamCaptureModeThreadLocal));
+    LO_HIP(m, hipStreamBeginCapture(m->stream, hipStreamCaptureModeThreadLocal));
     const int* dn = M.prm_n;
     const dim3 grid(std::max(1, std::min(1024, (M.NP + kPar - 1) / kPar)));
     const dim3 tgrid(std::max(1, std::min(1024, (M.NP + 63) / 64)));
@@ -1489,8 +1482,8 @@ static int dm_update(lo_devmap* m, int n_host, bool from_scan, const float T[12]
     P.from_scan = from_scan ? 1 : 0;
     ++m->updates;
     hipLaunchKernelGGL(k_dm_setprm, dim3(1), dim3(64), 0, m->stream, M, P);
-    DM_HIP(m, hipGetLastError());
-    DM_HIP(m, hipGraphLaunch(m->gexec, m->stream));
+    LO_HIP(m, hipGetLastError());
+    LO_HIP(m, hipGraphLaunch(m->gexec, m->stream));
     return LO_OK;
 }
 
@@ -1499,16 +1492,16 @@ int lo_devmap_update(lo_devmap* m, const float* world_xyz, size_t n, int on_devi
     if (!m || !sensor || (n > 0 && !world_xyz)) return LO_ERR_ARG;
     if (n == 0 || !is_keyframe) return LO_OK;           // UpdateVoxelMap returns before pruning (:135-142)
     if (n > static_cast<size_t>(m->M.NP)) { m->err = "more points than max_points"; return LO_ERR_CAPACITY; }
-    DM_HIP(m, hipSetDevice(m->device));
+    LO_HIP(m, hipSetDevice(m->device));
     dm_stream(m);
-    DM_HIP(m, hipMemcpyAsync(m->d_in, world_xyz, n * 3 * sizeof(float),
+    LO_HIP(m, hipMemcpyAsync(m->d_in, world_xyz, n * 3 * sizeof(float),
                              on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, m->stream));
     return dm_update(m, static_cast<int>(n), false, nullptr, sensor, max_distance);
 }
 
 int lo_devmap_update_from_scan(lo_devmap* m, const float T[12], double max_distance) {
     if (!m || !T) return LO_ERR_ARG;
-    DM_HIP(m, hipSetDevice(m->device));
+    LO_HIP(m, hipSetDevice(m->device));
     dm_stream(m);
     const double sensor[3] = {T[3], T[7], T[11]};        // Vector3f -> Vector3d
     // an empty scan returns before the prune (UpdateVoxelMap :135-137): the kernels read the device count
@@ -1517,7 +1510,7 @@ int lo_devmap_update_from_scan(lo_devmap* m, const float T[12], double max_dista
 
 int lo_devmap_apply_transform(lo_devmap* m, const float T[12]) {
     if (!m || !T) return LO_ERR_ARG;
-    DM_HIP(m, hipSetDevice(m->device));
+    LO_HIP(m, hipSetDevice(m->device));
     dm_stream(m);
     int rc = dm_bind_table(m);
     if (rc != LO_OK) return rc;
@@ -1535,23 +1528,23 @@ int lo_devmap_apply_transform(lo_devmap* m, const float T[12]) {
     hipLaunchKernelGGL(k_dm_flag, dim3(1), dim3(64), 0, m->stream, M, static_cast<int>(R_TAB));
     hipLaunchKernelGGL(k_dm_rebuild_clear, dim3(1024), dim3(kPar), 0, m->stream, M);
     hipLaunchKernelGGL(k_dm_rebuild_fill, dim3(1024), dim3(kPar), 0, m->stream, M);
-    DM_HIP(m, hipGetLastError());
+    LO_HIP(m, hipGetLastError());
     return LO_OK;
 }
 
 int lo_devmap_status(lo_devmap* m) {
     if (!m) return LO_ERR_ARG;
-    DM_HIP(m, hipSetDevice(m->device));
+    LO_HIP(m, hipSetDevice(m->device));
     dm_stream(m);
-    DM_HIP(m, hipMemcpyAsync(m->h_cnt, m->M.cnt, 16 * sizeof(int), hipMemcpyDeviceToHost, m->stream));
-    DM_HIP(m, hipStreamSynchronize(m->stream));
+    LO_HIP(m, hipMemcpyAsync(m->h_cnt, m->M.cnt, 16 * sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    LO_HIP(m, hipStreamSynchronize(m->stream));
     if (m->h_cnt[C_ERR]) { m->err = "device map overflow / invalid key (error bits " + std::to_string(m->h_cnt[C_ERR]) + ")"; return LO_ERR_CAPACITY; }
     return LO_OK;
 }
 
 int lo_devmap_sync_points(lo_devmap* m) {
     if (!m) return LO_ERR_ARG;
-    DM_HIP(m, hipSetDevice(m->device));
+    LO_HIP(m, hipSetDevice(m->device));
     dm_stream(m);
     const int rc = ctx_grid_from_device(m->ctx, m->M.c0, m->M.cnt + C_N0, static_cast<size_t>(m->M.C0));
     if (rc != LO_OK) m->err = std::string("sync_points: ") + lo_last_error(m->ctx);
@@ -1560,10 +1553,10 @@ int lo_devmap_sync_points(lo_devmap* m) {
 
 int lo_devmap_status_async(lo_devmap* m) {
     if (!m) return LO_ERR_ARG;
-    DM_HIP(m, hipSetDevice(m->device));
+    LO_HIP(m, hipSetDevice(m->device));
     dm_stream(m);
-    DM_HIP(m, hipMemcpyAsync(m->h_err, m->M.cnt, 16 * sizeof(int), hipMemcpyDeviceToHost, m->stream));
-    DM_HIP(m, hipEventRecord(m->ev_err, m->stream));
+    LO_HIP(m, hipMemcpyAsync(m->h_err, m->M.cnt, 16 * sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    LO_HIP(m, hipEventRecord(m->ev_err, m->stream));
     m->err_pending = true;
     return LO_OK;
 }
@@ -1573,7 +1566,7 @@ int lo_devmap_status_poll(lo_devmap* m) {
     if (!m->err_pending) return LO_OK;
     const hipError_t q = hipEventQuery(m->ev_err);
     if (q == hipErrorNotReady) return LO_OK;             // still in flight: the next poll reads it
-    DM_HIP(m, q);
+    LO_HIP(m, q);
     m->err_pending = false;
     if (m->h_err[C_ERR]) { m->err = "device map overflow / invalid key (error bits " + std::to_string(m->h_err[C_ERR]) + ")"; return LO_ERR_CAPACITY; }
     return LO_OK;
@@ -1581,17 +1574,17 @@ int lo_devmap_status_poll(lo_devmap* m) {
 
 int lo_devmap_counts(lo_devmap* m, size_t out[4]) {
     if (!m || !out) return LO_ERR_ARG;
-    DM_HIP(m, hipSetDevice(m->device));
+    LO_HIP(m, hipSetDevice(m->device));
     dm_stream(m);
-    DM_HIP(m, hipMemcpyAsync(m->h_cnt, m->M.cnt, 16 * sizeof(int), hipMemcpyDeviceToHost, m->stream));
-    DM_HIP(m, hipStreamSynchronize(m->stream));
+    LO_HIP(m, hipMemcpyAsync(m->h_cnt, m->M.cnt, 16 * sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    LO_HIP(m, hipStreamSynchronize(m->stream));
     out[0] = static_cast<size_t>(m->h_cnt[C_N0]);
     out[1] = static_cast<size_t>(m->h_cnt[C_N1]);
     out[3] = static_cast<size_t>(m->h_cnt[C_ERR]);
     // surfels: counted from the L1 flags
     const int n1 = m->h_cnt[C_N1];
     std::vector<int> has(std::max(n1, 1));
-    if (n1 > 0) DM_HIP(m, hipMemcpy(has.data(), m->M.has, n1 * sizeof(int), hipMemcpyDeviceToHost));
+    if (n1 > 0) LO_HIP(m, hipMemcpy(has.data(), m->M.has, n1 * sizeof(int), hipMemcpyDeviceToHost));
     size_t s = 0;
     for (int i = 0; i < n1; ++i) s += has[i] ? 1 : 0;
     out[2] = s;

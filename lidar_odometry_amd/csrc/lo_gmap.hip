@@ -25,6 +25,7 @@
 
 #include "../../include/lo_gmap.h"
 #include "../../include/lo_io.h"
+#include "lo_buf.h"
 #include "lo_ctx_internal.h"
 #include "lo_device.h"
 
@@ -189,22 +190,21 @@ struct lo_gmap {
     std::vector<Chunk> chunks;           // host mirror of d_chunks
     size_t n_points = 0;
     // device buffers, all sized at create
-    float* d_arena = nullptr;            // stored clouds, sensor frame
-    Chunk* d_chunks = nullptr;
-    float* d_poses = nullptr;            // max_keyframes x 12
-    float* d_world = nullptr;            // transformed concatenation (the voxel_size <= 0 result)
-    uint64_t* d_keys = nullptr;
-    uint64_t* d_skeys = nullptr;
-    uint32_t* d_iota = nullptr;          // 0..max_points-1, written once
-    uint32_t* d_sidx = nullptr;
-    uint32_t* d_flag = nullptr;          // max_points + 1
-    uint32_t* d_rid = nullptr;           // max_points + 1
-    uint32_t* d_starts = nullptr;        // max_points + 1
-    float* d_sorted = nullptr;
-    float* d_out = nullptr;
-    unsigned* d_counts = nullptr;        // [0] points out of range, [1] voxels
-    void* d_tmp = nullptr;               // hipcub work space
-    size_t tmp_bytes = 0;
+    DevBuf<float> d_arena;               // stored clouds, sensor frame
+    DevBuf<Chunk> d_chunks;
+    DevBuf<float> d_poses;               // max_keyframes x 12
+    DevBuf<float> d_world;               // transformed concatenation (the voxel_size <= 0 result)
+    DevBuf<uint64_t> d_keys;
+    DevBuf<uint64_t> d_skeys;
+    DevBuf<uint32_t> d_iota;             // 0..max_points-1, written once
+    DevBuf<uint32_t> d_sidx;
+    DevBuf<uint32_t> d_flag;             // max_points + 1
+    DevBuf<uint32_t> d_rid;              // max_points + 1
+    DevBuf<uint32_t> d_starts;           // max_points + 1
+    DevBuf<float> d_sorted;
+    DevBuf<float> d_out;
+    DevBuf<unsigned> d_counts;           // [0] points out of range, [1] voxels
+    DevBuf<void> d_tmp;                  // hipcub work space
     // last build
     const float* d_result = nullptr;
     size_t n_result = 0;
@@ -212,14 +212,8 @@ struct lo_gmap {
     std::string err;
 };
 
-#define GM_HIP(m, x)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (x);                                                                  \
-        if (e_ != hipSuccess) { (m)->err = std::string(#x) + ": " + hipGetErrorString(e_); return LO_ERR_HIP; } \
-    } while (0)
-
 static int gm_enter(lo_gmap* m) {
-    GM_HIP(m, hipSetDevice(m->device));
+    LO_HIP(m, hipSetDevice(m->device));
     m->stream = static_cast<hipStream_t>(lo_stream(m->ctx));   // lo_set_stream may have replaced it
     return LO_OK;
 }
@@ -235,9 +229,9 @@ static int gm_push(lo_gmap* m, int64_t id, size_t n) {
                                   static_cast<int>(std::min<size_t>(kChunk, n - off)), 0});
     const size_t added = m->chunks.size() - first;             // <= max_chunks in total: n / kChunk + 1 per keyframe
     if (added > 0)
-        GM_HIP(m, hipMemcpyAsync(m->d_chunks + first, m->chunks.data() + first, added * sizeof(Chunk),
+        LO_HIP(m, hipMemcpyAsync(m->d_chunks + first, m->chunks.data() + first, added * sizeof(Chunk),
                                  hipMemcpyHostToDevice, m->stream));
-    GM_HIP(m, hipStreamSynchronize(m->stream));               // the caller's buffer is free again
+    LO_HIP(m, hipStreamSynchronize(m->stream));               // the caller's buffer is free again
     m->ids.push_back(id);
     m->n_points += n;
     return LO_OK;
@@ -254,37 +248,37 @@ static int gm_enqueue(lo_gmap* m, float voxel_size, hipEvent_t* ev) {
     const int n = static_cast<int>(m->n_points);
     const dim3 grid_t(static_cast<unsigned>(m->chunks.size())), blk(kBlock);
     const bool filter = voxel_size > 0.0f;
-    GM_HIP(m, hipMemsetAsync(m->d_counts, 0, 2 * sizeof(unsigned), m->stream));
-    if (ev) GM_HIP(m, hipEventRecord(ev[0], m->stream));
+    LO_HIP(m, hipMemsetAsync(m->d_counts, 0, 2 * sizeof(unsigned), m->stream));
+    if (ev) LO_HIP(m, hipEventRecord(ev[0], m->stream));
     if (!filter) {
         hipLaunchKernelGGL(k_gmap_transform<false>, grid_t, blk, 0, m->stream, m->d_arena, m->d_chunks, m->d_poses,
                            1.0f, m->d_world, m->d_keys, m->d_counts);
-        GM_HIP(m, hipGetLastError());
+        LO_HIP(m, hipGetLastError());
         if (ev)
-            for (int s = 1; s <= LO_GMAP_STAGES; ++s) GM_HIP(m, hipEventRecord(ev[s], m->stream));
+            for (int s = 1; s <= LO_GMAP_STAGES; ++s) LO_HIP(m, hipEventRecord(ev[s], m->stream));
         return LO_OK;
     }
     hipLaunchKernelGGL(k_gmap_transform<true>, grid_t, blk, 0, m->stream, m->d_arena, m->d_chunks, m->d_poses,
                        voxel_size, m->d_world, m->d_keys, m->d_counts);
-    GM_HIP(m, hipGetLastError());
-    if (ev) GM_HIP(m, hipEventRecord(ev[1], m->stream));
-    size_t t = m->tmp_bytes;
-    GM_HIP(m, hipcub::DeviceRadixSort::SortPairs(m->d_tmp, t, m->d_keys, m->d_skeys, m->d_iota, m->d_sidx, n, 0,
+    LO_HIP(m, hipGetLastError());
+    if (ev) LO_HIP(m, hipEventRecord(ev[1], m->stream));
+    size_t t = m->d_tmp.capacity();
+    LO_HIP(m, hipcub::DeviceRadixSort::SortPairs(m->d_tmp, t, m->d_keys.get(), m->d_skeys.get(), m->d_iota.get(), m->d_sidx.get(), n, 0,
                                                  kKeyBits, m->stream));
-    if (ev) GM_HIP(m, hipEventRecord(ev[2], m->stream));
+    if (ev) LO_HIP(m, hipEventRecord(ev[2], m->stream));
     const dim3 grid_n1(gm_blocks(static_cast<size_t>(n) + 1));
     hipLaunchKernelGGL(k_gmap_heads, grid_n1, blk, 0, m->stream, m->d_skeys, m->d_sidx, m->d_world, n, m->d_flag,
                        m->d_sorted);
-    GM_HIP(m, hipGetLastError());
-    t = m->tmp_bytes;
-    GM_HIP(m, hipcub::DeviceScan::ExclusiveSum(m->d_tmp, t, m->d_flag, m->d_rid, n + 1, m->stream));
+    LO_HIP(m, hipGetLastError());
+    t = m->d_tmp.capacity();
+    LO_HIP(m, hipcub::DeviceScan::ExclusiveSum(m->d_tmp, t, m->d_flag.get(), m->d_rid.get(), n + 1, m->stream));
     hipLaunchKernelGGL(k_gmap_starts, grid_n1, blk, 0, m->stream, m->d_flag, m->d_rid, n, m->d_starts, m->d_counts);
-    GM_HIP(m, hipGetLastError());
-    if (ev) GM_HIP(m, hipEventRecord(ev[3], m->stream));
+    LO_HIP(m, hipGetLastError());
+    if (ev) LO_HIP(m, hipEventRecord(ev[3], m->stream));
     hipLaunchKernelGGL(k_gmap_centroids, dim3(gm_blocks(n)), blk, 0, m->stream, m->d_sorted, m->d_starts, m->d_counts,
                        m->d_out);
-    GM_HIP(m, hipGetLastError());
-    if (ev) GM_HIP(m, hipEventRecord(ev[4], m->stream));
+    LO_HIP(m, hipGetLastError());
+    if (ev) LO_HIP(m, hipEventRecord(ev[4], m->stream));
     return LO_OK;
 }
 
@@ -294,7 +288,7 @@ static int gm_prepare(lo_gmap* m, const float* poses, size_t n_poses) {
     if (m->n_points == 0) return LO_INSUFFICIENT;
     const int rc = gm_enter(m);
     if (rc != LO_OK) return rc;
-    GM_HIP(m, hipMemcpyAsync(m->d_poses, poses, n_poses * 12 * sizeof(float), hipMemcpyHostToDevice, m->stream));
+    LO_HIP(m, hipMemcpyAsync(m->d_poses, poses, n_poses * 12 * sizeof(float), hipMemcpyHostToDevice, m->stream));
     return LO_OK;
 }
 
@@ -323,28 +317,27 @@ lo_gmap* lo_gmap_create(lo_ctx* ctx, size_t max_points, size_t max_keyframes, in
         const size_t np = max_points;
         const int ni = static_cast<int>(np);
         size_t t_sort = 0, t_scan = 0;
-        GM_HIP(m, hipcub::DeviceRadixSort::SortPairs(nullptr, t_sort, m->d_keys, m->d_skeys, m->d_iota, m->d_sidx, ni, 0,
+        LO_HIP(m, hipcub::DeviceRadixSort::SortPairs(nullptr, t_sort, m->d_keys.get(), m->d_skeys.get(), m->d_iota.get(), m->d_sidx.get(), ni, 0,
                                                      kKeyBits, m->stream));
-        GM_HIP(m, hipcub::DeviceScan::ExclusiveSum(nullptr, t_scan, m->d_flag, m->d_rid, ni + 1, m->stream));
-        m->tmp_bytes = std::max<size_t>(std::max(t_sort, t_scan), 256);
-        GM_HIP(m, hipMalloc(&m->d_arena, np * 3 * sizeof(float)));
-        GM_HIP(m, hipMalloc(&m->d_chunks, m->max_chunks * sizeof(Chunk)));
-        GM_HIP(m, hipMalloc(&m->d_poses, max_keyframes * 12 * sizeof(float)));
-        GM_HIP(m, hipMalloc(&m->d_world, np * 3 * sizeof(float)));
-        GM_HIP(m, hipMalloc(&m->d_keys, np * sizeof(uint64_t)));
-        GM_HIP(m, hipMalloc(&m->d_skeys, np * sizeof(uint64_t)));
-        GM_HIP(m, hipMalloc(&m->d_iota, np * sizeof(uint32_t)));
-        GM_HIP(m, hipMalloc(&m->d_sidx, np * sizeof(uint32_t)));
-        GM_HIP(m, hipMalloc(&m->d_flag, (np + 1) * sizeof(uint32_t)));
-        GM_HIP(m, hipMalloc(&m->d_rid, (np + 1) * sizeof(uint32_t)));
-        GM_HIP(m, hipMalloc(&m->d_starts, (np + 1) * sizeof(uint32_t)));
-        GM_HIP(m, hipMalloc(&m->d_sorted, np * 3 * sizeof(float)));
-        GM_HIP(m, hipMalloc(&m->d_out, np * 3 * sizeof(float)));
-        GM_HIP(m, hipMalloc(&m->d_counts, 2 * sizeof(unsigned)));
-        GM_HIP(m, hipMalloc(&m->d_tmp, m->tmp_bytes));
+        LO_HIP(m, hipcub::DeviceScan::ExclusiveSum(nullptr, t_scan, m->d_flag.get(), m->d_rid.get(), ni + 1, m->stream));
+        LO_HIP(m, m->d_arena.reserve(np * 3));
+        LO_HIP(m, m->d_chunks.reserve(m->max_chunks));
+        LO_HIP(m, m->d_poses.reserve(max_keyframes * 12));
+        LO_HIP(m, m->d_world.reserve(np * 3));
+        LO_HIP(m, m->d_keys.reserve(np));
+        LO_HIP(m, m->d_skeys.reserve(np));
+        LO_HIP(m, m->d_iota.reserve(np));
+        LO_HIP(m, m->d_sidx.reserve(np));
+        LO_HIP(m, m->d_flag.reserve(np + 1));
+        LO_HIP(m, m->d_rid.reserve(np + 1));
+        LO_HIP(m, m->d_starts.reserve(np + 1));
+        LO_HIP(m, m->d_sorted.reserve(np * 3));
+        LO_HIP(m, m->d_out.reserve(np * 3));
+        LO_HIP(m, m->d_counts.reserve(2));
+        LO_HIP(m, m->d_tmp.reserve(std::max<size_t>(std::max(t_sort, t_scan), 256)));
         hipLaunchKernelGGL(k_gmap_iota, dim3(gm_blocks(np)), dim3(kBlock), 0, m->stream, m->d_iota, np);
-        GM_HIP(m, hipGetLastError());
-        GM_HIP(m, hipStreamSynchronize(m->stream));
+        LO_HIP(m, hipGetLastError());
+        LO_HIP(m, hipStreamSynchronize(m->stream));
         return LO_OK;
     };
     const int rc = init();
@@ -357,15 +350,8 @@ lo_gmap* lo_gmap_create(lo_ctx* ctx, size_t max_points, size_t max_keyframes, in
 
 void lo_gmap_destroy(lo_gmap* m) {
     if (!m) return;
-    if (hipSetDevice(m->device) == hipSuccess) {
-        if (m->stream) (void)hipStreamSynchronize(static_cast<hipStream_t>(lo_stream(m->ctx)));
-        for (void* p : {static_cast<void*>(m->d_arena), static_cast<void*>(m->d_chunks), static_cast<void*>(m->d_poses),
-                        static_cast<void*>(m->d_world), static_cast<void*>(m->d_keys), static_cast<void*>(m->d_skeys),
-                        static_cast<void*>(m->d_iota), static_cast<void*>(m->d_sidx), static_cast<void*>(m->d_flag),
-                        static_cast<void*>(m->d_rid), static_cast<void*>(m->d_starts), static_cast<void*>(m->d_sorted),
-                        static_cast<void*>(m->d_out), static_cast<void*>(m->d_counts), m->d_tmp})
-            if (p) (void)hipFree(p);
-    }
+    if (hipSetDevice(m->device) == hipSuccess && m->stream)
+        (void)hipStreamSynchronize(static_cast<hipStream_t>(lo_stream(m->ctx)));
     delete m;
 }
 
@@ -389,7 +375,7 @@ int lo_gmap_add_keyframe(lo_gmap* m, int64_t id, const float* pts, size_t n, int
     if (rc == LO_OK) rc = gm_enter(m);
     if (rc != LO_OK) return rc;
     if (n > 0)
-        GM_HIP(m, hipMemcpyAsync(m->d_arena + 3 * m->n_points, pts, n * 3 * sizeof(float),
+        LO_HIP(m, hipMemcpyAsync(m->d_arena + 3 * m->n_points, pts, n * 3 * sizeof(float),
                                  on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, m->stream));
     return gm_push(m, id, n);
 }
@@ -406,13 +392,13 @@ int lo_gmap_add_from_scan(lo_gmap* m, int64_t id) {
     lo_config cfg;
     if (lo_get_config(m->ctx, &cfg) != LO_OK) return LO_ERR_ARG;
     int n = 0;
-    GM_HIP(m, hipMemcpyAsync(&n, d_scan_n, sizeof(int), hipMemcpyDeviceToHost, m->stream));
-    GM_HIP(m, hipStreamSynchronize(m->stream));
+    LO_HIP(m, hipMemcpyAsync(&n, d_scan_n, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    LO_HIP(m, hipStreamSynchronize(m->stream));
     if (n < 0 || n > cfg.max_points) { m->err = "filtered count beyond max_points"; return LO_ERR_STATE; }
     rc = gm_room(m, static_cast<size_t>(n));
     if (rc != LO_OK) return rc;
     if (n > 0)
-        GM_HIP(m, hipMemcpyAsync(m->d_arena + 3 * m->n_points, d_scan, static_cast<size_t>(n) * 3 * sizeof(float),
+        LO_HIP(m, hipMemcpyAsync(m->d_arena + 3 * m->n_points, d_scan, static_cast<size_t>(n) * 3 * sizeof(float),
                                  hipMemcpyDeviceToDevice, m->stream));
     return gm_push(m, id, static_cast<size_t>(n));
 }
@@ -426,8 +412,8 @@ int lo_gmap_build(lo_gmap* m, const float* poses, size_t n_poses, float voxel_si
     if (rc == LO_OK) rc = gm_enqueue(m, voxel_size, nullptr);
     if (rc != LO_OK) return rc;
     unsigned counts[2] = {0u, 0u};
-    GM_HIP(m, hipMemcpyAsync(counts, m->d_counts, sizeof(counts), hipMemcpyDeviceToHost, m->stream));
-    GM_HIP(m, hipStreamSynchronize(m->stream));
+    LO_HIP(m, hipMemcpyAsync(counts, m->d_counts, sizeof(counts), hipMemcpyDeviceToHost, m->stream));
+    LO_HIP(m, hipStreamSynchronize(m->stream));
     if (voxel_size > 0.0f) {
         if (counts[0] != 0u) {
             m->err = std::to_string(counts[0]) + " of " + std::to_string(m->n_points) +
@@ -451,8 +437,8 @@ long long lo_gmap_download(lo_gmap* m, float* out, size_t cap) {
     const size_t k = std::min(cap, m->n_result);
     const int rc = gm_enter(m);
     if (rc != LO_OK) return rc;
-    if (k > 0) GM_HIP(m, hipMemcpyAsync(out, m->d_result, k * 3 * sizeof(float), hipMemcpyDeviceToHost, m->stream));
-    GM_HIP(m, hipStreamSynchronize(m->stream));
+    if (k > 0) LO_HIP(m, hipMemcpyAsync(out, m->d_result, k * 3 * sizeof(float), hipMemcpyDeviceToHost, m->stream));
+    LO_HIP(m, hipStreamSynchronize(m->stream));
     return static_cast<long long>(k);
 }
 
@@ -486,7 +472,7 @@ int lo_gmap_bench_build(lo_gmap* m, const float* poses, size_t n_poses, float vo
     m->d_result = nullptr;                                     // the timed builds are not checked: no result
     m->n_result = 0;
     hipEvent_t ev[LO_GMAP_STAGES + 1];
-    for (hipEvent_t& e : ev) GM_HIP(m, hipEventCreate(&e));
+    for (hipEvent_t& e : ev) LO_HIP(m, hipEventCreate(&e));
     auto done = [&](int r) {
         for (hipEvent_t& e : ev) (void)hipEventDestroy(e);
         return r;

@@ -1,0 +1,302 @@
+// lo_grid.hip — the KDTree variant's point grid: built on the host (grid_build, all_pairs_upload; lo_map_set_points)
+// or on the device from a device map's centroids (ctx_grid_from_device and its k_grid_* kernels).
+#include <hipcub/hipcub.hpp>
+
+#include "lo_ctx_def.h"
+
+// VoxelMap::RebuildKdTree (VoxelMap.cpp:420-438) equivalent: a dense uniform grid (cell = 2 x voxel, doubled
+// until it fits kKdMaxCells) over the L0 centroids in GetPointCloud order; points sorted by cell (x fastest),
+// index order inside a cell; kd_start[cell] = first point, kd_start[ncell] = m.
+static constexpr size_t kKdMaxCells = size_t(1) << 26;
+
+namespace lo {
+// with_order: also the reference kd-tree's visit order (the tie-break of equal distances); without it the kNN
+// kernels flag a deciding tie in DevState::kd_tie instead of ranking it (the loop-closure ICP then rebuilds with it).
+// min_per_cell > 0 (the loop-closure ICP's matched keyframe cloud): the cell edge doubles (up to 3 times) while the
+// occupied cells hold fewer than min_per_cell points on average -- a voxel-filtered, strided keyframe cloud is sparse
+// at 2 x voxel_size, so most queries would need the outer shells or the brute-force fallback.  The kNN result does
+// not depend on the edge (every answer is certified against the scanned cube); only the work per query does.
+int grid_build(lo_ctx* c, PointGrid& G, const float* xyz, size_t m, bool with_order, int min_per_cell) {
+    if (m > 0 && !xyz) { c->err = "null points"; return LO_ERR_ARG; }
+    if (m > static_cast<size_t>(INT32_MAX / 2)) { c->err = "too many map points"; return LO_ERR_CAPACITY; }
+    for (size_t i = 0; i < 3 * m; ++i)
+        if (!std::isfinite(xyz[i])) { c->err = "non-finite map point"; return LO_ERR_ARG; }
+    // the reference kd-tree's visit order over the same cloud (equal-distance neighbours are ranked by it): built
+    // on a second host thread while this one builds the grid (nanoflann's partition passes are branch-bound,
+    // ~0.3 ms for a 3.6k-point keyframe cloud, as the reference's own buildIndex per loop-closure call)
+    std::vector<KdNode> nodes;
+    std::vector<uint32_t> vpos;
+    std::thread order_thread([&] { if (with_order) KdOrderBuilder(xyz, m).build(nodes, vpos); });
+    struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{order_thread};
+    float h = 2.0f * c->cfg.voxel_size;
+    int org[3] = {0, 0, 0}, dim[3] = {1, 1, 1};
+    auto cell = [&](float v) { return static_cast<int64_t>(std::floor(v / h)); };
+    std::vector<uint32_t> start, lin(m);
+    for (int grow = 0;; ++grow) {
+    for (;;) {
+        int64_t lo[3] = {INT64_MAX, INT64_MAX, INT64_MAX}, hi[3] = {INT64_MIN, INT64_MIN, INT64_MIN};
+        for (size_t i = 0; i < m; ++i)
+            for (int a = 0; a < 3; ++a) { const int64_t k = cell(xyz[3 * i + a]); lo[a] = std::min(lo[a], k); hi[a] = std::max(hi[a], k); }
+        if (m == 0) { for (int a = 0; a < 3; ++a) { lo[a] = 0; hi[a] = 0; } }
+        size_t ncell = 1;
+        bool ok = true;
+        for (int a = 0; a < 3; ++a) {
+            const int64_t d = hi[a] - lo[a] + 1;
+            if (d > static_cast<int64_t>(kKdMaxCells) || lo[a] < INT32_MIN / 2 || hi[a] > INT32_MAX / 2) { ok = false; break; }
+            ncell *= static_cast<size_t>(d);
+            if (ncell > kKdMaxCells) { ok = false; break; }
+        }
+        if (ok) { for (int a = 0; a < 3; ++a) { org[a] = static_cast<int>(lo[a]); dim[a] = static_cast<int>(hi[a] - lo[a] + 1); } break; }
+        h *= 2.0f;
+    }
+    const size_t ncell = static_cast<size_t>(dim[0]) * dim[1] * dim[2];
+    start.assign(ncell + 1, 0);
+    size_t occupied = 0;
+    for (size_t i = 0; i < m; ++i) {
+        const int64_t x = cell(xyz[3 * i]) - org[0], y = cell(xyz[3 * i + 1]) - org[1], z = cell(xyz[3 * i + 2]) - org[2];
+        lin[i] = static_cast<uint32_t>((static_cast<size_t>(z) * dim[1] + y) * dim[0] + x);
+        occupied += start[lin[i] + 1]++ == 0;
+    }
+    if (min_per_cell > 0 && grow < 3 && m >= 64 && occupied * static_cast<size_t>(min_per_cell) > m) { h *= 2.0f; continue; }
+    break;
+    }
+    const size_t ncell = static_cast<size_t>(dim[0]) * dim[1] * dim[2];
+    for (size_t k = 0; k < ncell; ++k) start[k + 1] += start[k];
+    std::vector<float4> pts(std::max<size_t>(m, 1));
+    std::vector<uint32_t> fill(start.begin(), start.end() - 1);
+    for (size_t i = 0; i < m; ++i) {                     // stable: index order inside a cell
+        float4 v;
+        v.x = xyz[3 * i]; v.y = xyz[3 * i + 1]; v.z = xyz[3 * i + 2];
+        int32_t id = static_cast<int32_t>(i);
+        std::memcpy(&v.w, &id, sizeof(float));
+        pts[fill[lin[i]]++] = v;
+    }
+    LO_HIP(c, hipSetDevice(c->device));
+    LO_HIP(c, hipStreamSynchronize(c->stream));
+    LO_HIP(c, G.d_pts.reserve(pts.size()));
+    LO_HIP(c, G.d_start.reserve(start.size()));
+    order_thread.join();
+    if (nodes.empty()) nodes.push_back(KdNode{-1, -1, 0, 0, 0.0f, 0.0f});
+    if (vpos.empty()) vpos.push_back(0);
+    LO_HIP(c, G.d_vpos.reserve(vpos.size()));
+    LO_HIP(c, G.d_nodes.reserve(nodes.size()));
+    // one pinned staging buffer, four async copies on the context stream (the kernels that read the grid follow
+    // in stream order; the next grid_build's stream sync retires the copies before the buffer is refilled)
+    const size_t b_pts = pts.size() * sizeof(float4), b_start = start.size() * sizeof(uint32_t);
+    const size_t b_vpos = vpos.size() * sizeof(uint32_t), b_nodes = nodes.size() * sizeof(KdNode);
+    const size_t total = b_pts + b_start + b_vpos + b_nodes;
+    if (total > G.h_stage.capacity()) LO_HIP(c, G.h_stage.reserve(2 * total));
+    char* hs = static_cast<char*>(G.h_stage.get());
+    std::memcpy(hs, pts.data(), b_pts);
+    std::memcpy(hs + b_pts, start.data(), b_start);
+    std::memcpy(hs + b_pts + b_start, vpos.data(), b_vpos);
+    std::memcpy(hs + b_pts + b_start + b_vpos, nodes.data(), b_nodes);
+    LO_HIP(c, hipMemcpyAsync(G.d_pts, hs, b_pts, hipMemcpyHostToDevice, c->stream));
+    LO_HIP(c, hipMemcpyAsync(G.d_start, hs + b_pts, b_start, hipMemcpyHostToDevice, c->stream));
+    LO_HIP(c, hipMemcpyAsync(G.d_vpos, hs + b_pts + b_start, b_vpos, hipMemcpyHostToDevice, c->stream));
+    LO_HIP(c, hipMemcpyAsync(G.d_nodes, hs + b_pts + b_start + b_vpos, b_nodes, hipMemcpyHostToDevice, c->stream));
+    G.m = static_cast<int>(m);
+    G.has_order = with_order;
+    G.all = false;
+    G.h = h;
+    for (int a = 0; a < 3; ++a) { G.org[a] = org[a]; G.dim[a] = dim[a]; }
+    return LO_OK;
+}
+
+// A small point set (<= kKnnAllMax) for the all-pairs kernels (k_knn_all, k_inlier_all): the points in index order as
+// float4 (x, y, z, index), no cells and no visit order; with q (nq points) also the query cloud into c->d_pts, both
+// through the grid's pinned staging buffer (two async copies, no pageable-memory copy).
+int all_pairs_upload(lo_ctx* c, PointGrid& G, const float* xyz, size_t m, const float* q, size_t nq) {
+    if (m > static_cast<size_t>(kKnnAllMax)) { c->err = "all_pairs_upload: too many points"; return LO_ERR_CAPACITY; }
+    if (m > 0 && !xyz) { c->err = "null points"; return LO_ERR_ARG; }
+    for (size_t i = 0; i < 3 * m; ++i)
+        if (!std::isfinite(xyz[i])) { c->err = "non-finite map point"; return LO_ERR_ARG; }
+    LO_HIP(c, hipSetDevice(c->device));
+    LO_HIP(c, hipStreamSynchronize(c->stream));          // the staging buffer's previous copy has retired
+    const size_t mm = std::max<size_t>(m, 1), bytes = mm * sizeof(float4) + nq * 3 * sizeof(float);
+    LO_HIP(c, G.d_pts.reserve(mm));
+    if (bytes > G.h_stage.capacity()) LO_HIP(c, G.h_stage.reserve(2 * bytes));
+    float4* hs = static_cast<float4*>(G.h_stage.get());
+    for (size_t i = 0; i < m; ++i) {
+        int32_t id = static_cast<int32_t>(i);
+        float w;
+        std::memcpy(&w, &id, sizeof(float));
+        hs[i] = make_float4(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], w);
+    }
+    if (m > 0) LO_HIP(c, hipMemcpyAsync(G.d_pts, hs, m * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    if (nq > 0) {
+        float* hq = reinterpret_cast<float*>(hs + mm);
+        std::memcpy(hq, q, nq * 3 * sizeof(float));
+        LO_HIP(c, hipMemcpyAsync(c->d_pts, hq, nq * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    }
+    G.m = static_cast<int>(m);
+    G.has_order = false;
+    G.all = true;
+    return LO_OK;
+}
+}  // namespace lo
+
+namespace lo {
+// ---- the same grid built on the device (ctx_grid_from_device: the device map's L0 centroids) ----
+// Every kernel here clamps the device count to the array's capacity: a corrupt or overflowing count is reported by the
+// host (out[6] carries the raw count) without a read past the array.
+__global__ __launch_bounds__(1024) void k_grid_bounds(const float* __restrict__ xyz, const int* __restrict__ d_count,
+                                                     int cap, float* __restrict__ out) {
+    __shared__ float s[6][16];
+    const int m_raw = *d_count, m = min(max(m_raw, 0), cap), tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int i = tid; i < m; i += 1024)
+        for (int a = 0; a < 3; ++a) { const float v = xyz[3 * i + a]; lo[a] = fminf(lo[a], v); hi[a] = fmaxf(hi[a], v); }
+    for (int o = 32; o > 0; o >>= 1)
+        for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], __shfl_xor(lo[a], o, 64)); hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o, 64)); }
+    if (lane == 0) for (int a = 0; a < 3; ++a) { s[a][wid] = lo[a]; s[3 + a][wid] = hi[a]; }
+    __syncthreads();
+    if (tid < 6) {
+        float r = s[tid][0];
+        for (int w = 1; w < 16; ++w) r = tid < 3 ? fminf(r, s[tid][w]) : fmaxf(r, s[tid][w]);
+        out[tid] = r;
+    }
+    if (tid == 0) out[6] = __int_as_float(m_raw);
+}
+struct GridGeom {
+    float h;
+    int org[3], dim[3];
+};
+// grid_build's cell of a coordinate: floor(v / h) in fp32, as an int64 (the same operations)
+__device__ __forceinline__ long long grid_cell(float v, float h) { return static_cast<long long>(floorf(v / h)); }
+__global__ void k_grid_keys(const float* __restrict__ xyz, const int* __restrict__ d_count, int cap, GridGeom g,
+                            uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t* __restrict__ counts) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= min(*d_count, cap)) return;
+    const long long x = grid_cell(xyz[3 * i], g.h) - g.org[0], y = grid_cell(xyz[3 * i + 1], g.h) - g.org[1],
+                    z = grid_cell(xyz[3 * i + 2], g.h) - g.org[2];
+    const uint32_t lin = static_cast<uint32_t>((static_cast<unsigned long long>(z) * g.dim[1] + y) * g.dim[0] + x);
+    keys[i] = lin;
+    vals[i] = static_cast<uint32_t>(i);
+    atomicAdd(&counts[lin], 1u);
+}
+__global__ void k_grid_scatter(const float* __restrict__ xyz, const int* __restrict__ d_count, int cap,
+                               const uint32_t* __restrict__ svals, float4* __restrict__ pts) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= min(*d_count, cap)) return;
+    const uint32_t i = svals[p];
+    pts[p] = make_float4(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], __int_as_float(static_cast<int>(i)));
+}
+
+int ctx_grid_from_device(lo_ctx* c, const float* d_xyz, const int* d_count, size_t cap) {
+    if (!c || !d_xyz || !d_count) return LO_ERR_ARG;
+    if (!c->kd) { c->err = "ctx_grid_from_device: a KDTree-mode context"; return LO_ERR_STATE; }
+    LO_HIP(c, hipSetDevice(c->device));
+    PointGrid& G = c->grid;
+    DevGridScratch& S = c->gscr;
+    LO_HIP(c, S.d_bounds.reserve(8));
+    LO_HIP(c, S.h_bounds.reserve(8));
+    const int capi = static_cast<int>(std::min(cap, static_cast<size_t>(INT32_MAX)));
+    hipLaunchKernelGGL(k_grid_bounds, dim3(1), dim3(1024), 0, c->stream, d_xyz, d_count, capi, S.d_bounds);
+    LO_HIP(c, hipMemcpyAsync(S.h_bounds, S.d_bounds, 8 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    LO_HIP(c, hipStreamSynchronize(c->stream));
+    int mi = 0;
+    std::memcpy(&mi, &S.h_bounds[6], sizeof(int));
+    const size_t m = static_cast<size_t>(std::max(mi, 0));
+    if (m > cap) { c->err = "ctx_grid_from_device: count beyond the array"; return LO_ERR_CAPACITY; }
+    // grid_build's geometry loop, from the bounds (floor(v / h) is monotone in v, so the cells' extremes are the
+    // extremes' cells)
+    float h = 2.0f * c->cfg.voxel_size;
+    int org[3] = {0, 0, 0}, dim[3] = {1, 1, 1};
+    auto cell = [&](float v) { return static_cast<int64_t>(std::floor(v / h)); };
+    for (;;) {
+        int64_t lo[3], hi[3];
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = m ? cell(S.h_bounds[a]) : 0;
+            hi[a] = m ? cell(S.h_bounds[3 + a]) : 0;
+        }
+        size_t ncell = 1;
+        bool ok = true;
+        for (int a = 0; a < 3; ++a) {
+            const int64_t d = hi[a] - lo[a] + 1;
+            if (d > static_cast<int64_t>(kKdMaxCells) || lo[a] < INT32_MIN / 2 || hi[a] > INT32_MAX / 2) { ok = false; break; }
+            ncell *= static_cast<size_t>(d);
+            if (ncell > kKdMaxCells) { ok = false; break; }
+        }
+        if (ok) { for (int a = 0; a < 3; ++a) { org[a] = static_cast<int>(lo[a]); dim[a] = static_cast<int>(hi[a] - lo[a] + 1); } break; }
+        h *= 2.0f;
+    }
+    const size_t ncell = static_cast<size_t>(dim[0]) * dim[1] * dim[2];
+    const size_t mm = std::max<size_t>(m, 1);
+    LO_HIP(c, G.d_pts.reserve(mm));
+    LO_HIP(c, G.d_start.reserve(ncell + 1));
+    LO_HIP(c, S.d_keys.reserve(4 * mm));                 // keys, vals, sorted keys, sorted vals
+    LO_HIP(c, S.d_counts.reserve(ncell + 1));
+    uint32_t *keys = S.d_keys, *vals = keys + mm, *skeys = vals + mm, *svals = skeys + mm;
+    int bits = 1;
+    while (bits < 32 && (size_t(1) << bits) < ncell) ++bits;
+    size_t tmp_sort = 0, tmp_scan = 0;
+    LO_HIP(c, hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_sort, keys, skeys, vals, svals, static_cast<int>(mm), 0, bits,
+                                                 c->stream));
+    LO_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_scan, S.d_counts.get(), G.d_start.get(), static_cast<int>(ncell + 1),
+                                               c->stream));
+    LO_HIP(c, S.d_tmp.reserve(std::max(tmp_sort, tmp_scan)));
+    LO_HIP(c, hipMemsetAsync(S.d_counts, 0, (ncell + 1) * sizeof(uint32_t), c->stream));
+    GridGeom g{h, {org[0], org[1], org[2]}, {dim[0], dim[1], dim[2]}};
+    if (m > 0) {
+        const dim3 grid((m + 255) / 256), blk(256);
+        hipLaunchKernelGGL(k_grid_keys, grid, blk, 0, c->stream, d_xyz, d_count, capi, g, keys, vals, S.d_counts);
+        size_t t = S.d_tmp.capacity();
+        LO_HIP(c, hipcub::DeviceRadixSort::SortPairs(S.d_tmp, t, keys, skeys, vals, svals, static_cast<int>(m), 0, bits,
+                                                     c->stream));
+        hipLaunchKernelGGL(k_grid_scatter, grid, blk, 0, c->stream, d_xyz, d_count, capi, svals, G.d_pts);
+    }
+    size_t t2 = S.d_tmp.capacity();                           // start[cell] = points in the cells before it; start[ncell] = m
+    LO_HIP(c, hipcub::DeviceScan::ExclusiveSum(S.d_tmp, t2, S.d_counts.get(), G.d_start.get(), static_cast<int>(ncell + 1), c->stream));
+    LO_HIP(c, hipGetLastError());
+    G.m = static_cast<int>(m);
+    G.has_order = false;
+    G.all = false;
+    G.h = h;
+    for (int a = 0; a < 3; ++a) { G.org[a] = org[a]; G.dim[a] = dim[a]; }
+    c->grid_dev = true;
+    return LO_OK;
+}
+
+}  // namespace lo
+
+extern "C" {
+
+int lo_map_set_points(lo_ctx* c, const float* xyz, size_t m) {
+    if (!c) return LO_ERR_ARG;
+    if (!c->kd) { c->err = "lo_map_set_points needs use_surfel_correspondence = 0"; return LO_ERR_STATE; }
+    c->grid_dev = false;
+    return grid_build(c, c->grid, xyz, m);
+}
+
+}  // extern "C"
+
+namespace lo {
+// The kd visit order for a device-built grid (ctx_grid_from_device): its points back in index order (each grid
+// point carries its index), then the host build with the order -- the same grid plus the order.
+int grid_add_order(lo_ctx* c) {
+    PointGrid& G = c->grid;
+    const size_t m = static_cast<size_t>(G.m);
+    std::vector<float4> p(std::max<size_t>(m, 1));
+    LO_HIP(c, hipStreamSynchronize(c->stream));
+    if (m > 0) LO_HIP(c, hipMemcpy(p.data(), G.d_pts, m * sizeof(float4), hipMemcpyDeviceToHost));
+    std::vector<float> xyz(3 * std::max<size_t>(m, 1));
+    for (size_t k = 0; k < m; ++k) {
+        int i;
+        std::memcpy(&i, &p[k].w, sizeof(int));
+        if (i < 0 || static_cast<size_t>(i) >= m) { c->err = "device grid: bad point index"; return LO_ERR_STATE; }
+        xyz[3 * i] = p[k].x; xyz[3 * i + 1] = p[k].y; xyz[3 * i + 2] = p[k].z;
+    }
+    const int rc = grid_build(c, G, xyz.data(), m, true);
+    if (rc == LO_OK) c->grid_dev = true;                 // still the device map's grid (the next keyframe rebuilds it)
+    return rc;
+}
+}  // namespace lo
+
+extern "C" {
+
+int lo_kd_reruns(const lo_ctx* c) { return c ? c->kd_reruns : -1; }
+
+size_t lo_map_point_count(const lo_ctx* c) { return c ? static_cast<size_t>(c->grid.m) : 0; }
+
+}  // extern "C"

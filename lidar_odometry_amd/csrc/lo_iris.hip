@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/lo_iris.h"
+#include "lo_buf.h"
 #include "lo_ctx_internal.h"
 
 namespace lo {
@@ -216,26 +217,19 @@ struct lo_iris {
     size_t capacity = 0;
     std::vector<int64_t> ids;
     std::vector<float> pos;
-    uint64_t* d_db = nullptr;            // capacity + 1 descriptors; the last is the query's
-    uint32_t* d_img = nullptr;
-    double2* d_h = nullptr;
-    float* d_pts = nullptr;              // staging of host clouds
-    size_t pts_cap = 0;
-    float* d_dist = nullptr;             // per-entry match records
-    int* d_rec = nullptr;                // bias, diff, total: 3 x capacity
+    DevBuf<uint64_t> d_db;               // capacity + 1 descriptors; the last is the query's
+    DevBuf<uint32_t> d_img;
+    DevBuf<double2> d_h;
+    DevBuf<float> d_pts;                 // staging of host clouds
+    DevBuf<float> d_dist;                // per-entry match records
+    DevBuf<int> d_rec;                   // bias, diff, total: 3 x capacity
     bool has_query = false;
     std::vector<float> h_dist;
     std::string err;
 };
 
-#define IR_HIP(m, x)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (x);                                                                  \
-        if (e_ != hipSuccess) { (m)->err = std::string(#x) + ": " + hipGetErrorString(e_); return LO_ERR_HIP; } \
-    } while (0)
-
 static int ir_enter(lo_iris* m) {
-    IR_HIP(m, hipSetDevice(m->device));
+    LO_HIP(m, hipSetDevice(m->device));
     m->stream = static_cast<hipStream_t>(lo_stream(m->ctx));   // lo_set_stream may have replaced it
     return LO_OK;
 }
@@ -247,32 +241,25 @@ static int ir_image(lo_iris* m, const float* pts, size_t n, int on_device) {
     if (n > static_cast<size_t>(INT_MAX) / 3) { m->err = "too many points"; return LO_ERR_ARG; }
     const float* d = pts;
     if (!on_device && n > 0) {
-        if (n > m->pts_cap) {
-            if (m->d_pts) IR_HIP(m, hipFree(m->d_pts));
-            m->d_pts = nullptr;
-            m->pts_cap = 0;
-            const size_t cap = std::max<size_t>(2 * n, 1 << 16);
-            IR_HIP(m, hipMalloc(&m->d_pts, cap * 3 * sizeof(float)));
-            m->pts_cap = cap;
-        }
-        IR_HIP(m, hipMemcpyAsync(m->d_pts, pts, n * 3 * sizeof(float), hipMemcpyHostToDevice, m->stream));
+        if (3 * n > m->d_pts.capacity()) LO_HIP(m, m->d_pts.reserve(3 * std::max<size_t>(2 * n, 1 << 16)));
+        LO_HIP(m, hipMemcpyAsync(m->d_pts, pts, n * 3 * sizeof(float), hipMemcpyHostToDevice, m->stream));
         d = m->d_pts;
     }
-    IR_HIP(m, hipMemsetAsync(m->d_img, 0, kImgWords * sizeof(uint32_t), m->stream));
+    LO_HIP(m, hipMemsetAsync(m->d_img, 0, kImgWords * sizeof(uint32_t), m->stream));
     if (n > 0) {
         const int blocks = static_cast<int>(std::min<size_t>(1024, (n + 255) / 256));
         hipLaunchKernelGGL(k_iris_image, dim3(blocks), dim3(256), 0, m->stream, d, static_cast<int>(n), m->d_img);
-        IR_HIP(m, hipGetLastError());
+        LO_HIP(m, hipGetLastError());
     }
     return LO_OK;
 }
 
 // d_img -> the packed descriptor in slot
 static int ir_encode(lo_iris* m, uint64_t* slot) {
-    IR_HIP(m, hipMemsetAsync(slot, 0, kDescWords * sizeof(uint64_t), m->stream));
+    LO_HIP(m, hipMemsetAsync(slot, 0, kDescWords * sizeof(uint64_t), m->stream));
     hipLaunchKernelGGL(k_iris_encode, dim3(kRows, kScales), dim3(kThreads), 0, m->stream, m->d_img, m->d_h,
                        reinterpret_cast<uint32_t*>(slot));
-    IR_HIP(m, hipGetLastError());
+    LO_HIP(m, hipGetLastError());
     return LO_OK;
 }
 
@@ -287,7 +274,7 @@ static int ir_match(lo_iris* m) {
     int* r = m->d_rec;
     hipLaunchKernelGGL(k_iris_match, dim3((n_db + kEntries - 1) / kEntries), dim3(kThreads), 0, m->stream, m->d_db,
                        ir_slot(m, m->capacity), n_db, m->d_dist, r, r + m->capacity, r + 2 * m->capacity);
-    IR_HIP(m, hipGetLastError());
+    LO_HIP(m, hipGetLastError());
     return LO_OK;
 }
 
@@ -316,14 +303,14 @@ lo_iris* lo_iris_create(lo_ctx* ctx, size_t capacity, int* err) {
     auto init = [&]() -> int {
         int rc = ir_enter(m);
         if (rc != LO_OK) return rc;
-        IR_HIP(m, hipMalloc(&m->d_db, (capacity + 1) * kDescWords * sizeof(uint64_t)));
-        IR_HIP(m, hipMalloc(&m->d_img, kImgWords * sizeof(uint32_t)));
-        IR_HIP(m, hipMalloc(&m->d_h, static_cast<size_t>(kScales) * kCols * sizeof(double2)));
-        IR_HIP(m, hipMalloc(&m->d_dist, capacity * sizeof(float)));
-        IR_HIP(m, hipMalloc(&m->d_rec, 3 * capacity * sizeof(int)));
+        LO_HIP(m, m->d_db.reserve((capacity + 1) * kDescWords));
+        LO_HIP(m, m->d_img.reserve(kImgWords));
+        LO_HIP(m, m->d_h.reserve(static_cast<size_t>(kScales) * kCols));
+        LO_HIP(m, m->d_dist.reserve(capacity));
+        LO_HIP(m, m->d_rec.reserve(3 * capacity));
         std::vector<double> h;
         build_kernels(h);
-        IR_HIP(m, hipMemcpy(m->d_h, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+        LO_HIP(m, hipMemcpy(m->d_h, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
         return LO_OK;
     };
     const int rc = init();
@@ -336,12 +323,8 @@ lo_iris* lo_iris_create(lo_ctx* ctx, size_t capacity, int* err) {
 
 void lo_iris_destroy(lo_iris* m) {
     if (!m) return;
-    if (hipSetDevice(m->device) == hipSuccess) {
-        if (m->stream) (void)hipStreamSynchronize(static_cast<hipStream_t>(lo_stream(m->ctx)));
-        for (void* p : {static_cast<void*>(m->d_db), static_cast<void*>(m->d_img), static_cast<void*>(m->d_h),
-                        static_cast<void*>(m->d_pts), static_cast<void*>(m->d_dist), static_cast<void*>(m->d_rec)})
-            if (p) (void)hipFree(p);
-    }
+    if (hipSetDevice(m->device) == hipSuccess && m->stream)
+        (void)hipStreamSynchronize(static_cast<hipStream_t>(lo_stream(m->ctx)));
     delete m;
 }
 
@@ -361,8 +344,8 @@ int lo_iris_image(lo_iris* m, const float* pts, size_t n, uint8_t* out_img) {
     int rc = ir_enter(m);
     if (rc == LO_OK) rc = ir_image(m, pts, n, 0);
     if (rc != LO_OK) return rc;
-    IR_HIP(m, hipMemcpyAsync(out_img, m->d_img, kImgWords * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
-    IR_HIP(m, hipStreamSynchronize(m->stream));
+    LO_HIP(m, hipMemcpyAsync(out_img, m->d_img, kImgWords * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
+    LO_HIP(m, hipStreamSynchronize(m->stream));
     return LO_OK;
 }
 
@@ -371,13 +354,13 @@ int lo_iris_encode(lo_iris* m, const uint8_t* img, uint8_t* out_T, uint8_t* out_
     int rc = ir_enter(m);
     if (rc != LO_OK) return rc;
     m->has_query = false;                                  // the query slot is the scratch descriptor
-    IR_HIP(m, hipMemcpyAsync(m->d_img, img, kImgWords * sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
+    LO_HIP(m, hipMemcpyAsync(m->d_img, img, kImgWords * sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
     rc = ir_encode(m, ir_slot(m, m->capacity));
     if (rc != LO_OK) return rc;
     std::vector<uint64_t> d(kDescWords);
-    IR_HIP(m, hipMemcpyAsync(d.data(), ir_slot(m, m->capacity), kDescWords * sizeof(uint64_t), hipMemcpyDeviceToHost,
+    LO_HIP(m, hipMemcpyAsync(d.data(), ir_slot(m, m->capacity), kDescWords * sizeof(uint64_t), hipMemcpyDeviceToHost,
                              m->stream));
-    IR_HIP(m, hipStreamSynchronize(m->stream));
+    LO_HIP(m, hipStreamSynchronize(m->stream));
     for (int s = 0; s < kScales; ++s)
         for (int r = 0; r < kRows; ++r)
             for (int c = 0; c < kCols; ++c) {
@@ -402,7 +385,7 @@ int lo_iris_add_keyframe(lo_iris* m, int64_t id, const float position[3], const 
     if (rc == LO_OK) rc = ir_image(m, pts, n, on_device);
     if (rc == LO_OK) rc = ir_encode(m, ir_slot(m, m->ids.size()));
     if (rc != LO_OK) return rc;
-    IR_HIP(m, hipStreamSynchronize(m->stream));           // the caller's buffer (or the staging copy) is free again
+    LO_HIP(m, hipStreamSynchronize(m->stream));           // the caller's buffer (or the staging copy) is free again
     return ir_push(m, id, position);
 }
 
@@ -418,14 +401,14 @@ int lo_iris_add_from_scan(lo_iris* m, int64_t id, const float position[3]) {
     lo_config cfg;
     if (lo_get_config(m->ctx, &cfg) != LO_OK) return LO_ERR_ARG;
     int n = 0;
-    IR_HIP(m, hipMemcpyAsync(&n, d_scan_n, sizeof(int), hipMemcpyDeviceToHost, m->stream));
-    IR_HIP(m, hipStreamSynchronize(m->stream));
+    LO_HIP(m, hipMemcpyAsync(&n, d_scan_n, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    LO_HIP(m, hipStreamSynchronize(m->stream));
     if (n <= 0) return LO_INSUFFICIENT;
     if (n > cfg.max_points) { m->err = "filtered count beyond max_points"; return LO_ERR_STATE; }
     rc = ir_image(m, d_scan, static_cast<size_t>(n), 1);
     if (rc == LO_OK) rc = ir_encode(m, ir_slot(m, m->ids.size()));
     if (rc != LO_OK) return rc;
-    IR_HIP(m, hipStreamSynchronize(m->stream));
+    LO_HIP(m, hipStreamSynchronize(m->stream));
     return ir_push(m, id, position);
 }
 
@@ -443,12 +426,12 @@ int lo_iris_compare_all(lo_iris* m, const float* pts, size_t n, int on_device, f
         rc = ir_match(m);
         if (rc != LO_OK) return rc;
         const int* r = m->d_rec;
-        if (out_dist) IR_HIP(m, hipMemcpyAsync(out_dist, m->d_dist, k * sizeof(float), hipMemcpyDeviceToHost, m->stream));
-        if (out_bias) IR_HIP(m, hipMemcpyAsync(out_bias, r, k * sizeof(int), hipMemcpyDeviceToHost, m->stream));
-        if (out_diff) IR_HIP(m, hipMemcpyAsync(out_diff, r + m->capacity, k * sizeof(int), hipMemcpyDeviceToHost, m->stream));
-        if (out_total) IR_HIP(m, hipMemcpyAsync(out_total, r + 2 * m->capacity, k * sizeof(int), hipMemcpyDeviceToHost, m->stream));
+        if (out_dist) LO_HIP(m, hipMemcpyAsync(out_dist, m->d_dist, k * sizeof(float), hipMemcpyDeviceToHost, m->stream));
+        if (out_bias) LO_HIP(m, hipMemcpyAsync(out_bias, r, k * sizeof(int), hipMemcpyDeviceToHost, m->stream));
+        if (out_diff) LO_HIP(m, hipMemcpyAsync(out_diff, r + m->capacity, k * sizeof(int), hipMemcpyDeviceToHost, m->stream));
+        if (out_total) LO_HIP(m, hipMemcpyAsync(out_total, r + 2 * m->capacity, k * sizeof(int), hipMemcpyDeviceToHost, m->stream));
     }
-    IR_HIP(m, hipStreamSynchronize(m->stream));
+    LO_HIP(m, hipStreamSynchronize(m->stream));
     return LO_OK;
 }
 
@@ -494,14 +477,14 @@ int lo_iris_bench_match(lo_iris* m, int reps, float* avg_ms) {
     if (rc == LO_OK) rc = ir_match(m);                     // warm-up
     if (rc != LO_OK) return rc;
     hipEvent_t a, b;
-    IR_HIP(m, hipEventCreate(&a));
-    IR_HIP(m, hipEventCreate(&b));
-    IR_HIP(m, hipEventRecord(a, m->stream));
+    LO_HIP(m, hipEventCreate(&a));
+    LO_HIP(m, hipEventCreate(&b));
+    LO_HIP(m, hipEventRecord(a, m->stream));
     for (int i = 0; i < reps && rc == LO_OK; ++i) rc = ir_match(m);
-    IR_HIP(m, hipEventRecord(b, m->stream));
-    IR_HIP(m, hipEventSynchronize(b));
+    LO_HIP(m, hipEventRecord(b, m->stream));
+    LO_HIP(m, hipEventSynchronize(b));
     float ms = 0.0f;
-    IR_HIP(m, hipEventElapsedTime(&ms, a, b));
+    LO_HIP(m, hipEventElapsedTime(&ms, a, b));
     (void)hipEventDestroy(a);
     (void)hipEventDestroy(b);
     *avg_ms = ms / static_cast<float>(reps);

@@ -395,7 +395,7 @@ __global__ __launch_bounds__(256) void k_vf_wide(const float* __restrict__ samp,
     }
 }
 
-// ---------------------------------------------------------------- host side (called from lo_icp.hip)
+// ---------------------------------------------------------------- host side (called from lo_optimize.hip)
 // Grows the filter's buffers on the context stream s: the old buffers may still be read by filter launches
 // queued on s, so s (only) is drained before they are freed, and the table init runs on s, ordered before the
 // next k_vf_insert without a device-wide synchronisation that would stall other contexts sharing the GPU.
@@ -405,25 +405,23 @@ hipError_t vf_reserve(VfBuffers& b, size_t m, hipStream_t s) {
         hipError_t e0 = hipStreamSynchronize(s);
         if (e0 != hipSuccess) return e0;
     }
-    void* old[] = {b.tkey, b.tslot, b.sslot, b.samp, b.loc, b.blk, b.blk_pre, b.bucket, b.mid, b.big, b.ctr};
-    for (void* p : old) if (p) (void)hipFree(p);
-    b = VfBuffers{};
+    b = VfBuffers{};                                     // frees every old buffer before the first new one
     const size_t cap = std::max<size_t>(m, 4096);
     size_t tcap = 2;
     while (tcap < 2 * cap) tcap <<= 1;                  // load factor <= 0.5
     const size_t nb = (cap + kVfHeadsBlock - 1) / kVfHeadsBlock;
     hipError_t e;
-    if ((e = hipMalloc(&b.tkey, tcap * sizeof(uint64_t))) != hipSuccess) return e;
-    if ((e = hipMalloc(&b.tslot, tcap * sizeof(VfSlot))) != hipSuccess) return e;
-    if ((e = hipMalloc(&b.sslot, cap * sizeof(int32_t))) != hipSuccess) return e;
-    if ((e = hipMalloc(&b.samp, cap * 3 * sizeof(float))) != hipSuccess) return e;
-    if ((e = hipMalloc(&b.loc, cap * sizeof(int2))) != hipSuccess) return e;
-    if ((e = hipMalloc(&b.blk, nb * sizeof(int2))) != hipSuccess) return e;
-    if ((e = hipMalloc(&b.blk_pre, (nb + 1) * sizeof(int2))) != hipSuccess) return e;
-    if ((e = hipMalloc(&b.bucket, cap * sizeof(int32_t))) != hipSuccess) return e;
-    if ((e = hipMalloc(&b.mid, cap * sizeof(int32_t))) != hipSuccess) return e;
-    if ((e = hipMalloc(&b.big, cap * sizeof(int32_t))) != hipSuccess) return e;
-    if ((e = hipMalloc(&b.ctr, sizeof(VfCounters))) != hipSuccess) return e;
+    if ((e = b.tkey.reserve(tcap)) != hipSuccess) return e;
+    if ((e = b.tslot.reserve(tcap)) != hipSuccess) return e;
+    if ((e = b.sslot.reserve(cap)) != hipSuccess) return e;
+    if ((e = b.samp.reserve(cap * 3)) != hipSuccess) return e;
+    if ((e = b.loc.reserve(cap)) != hipSuccess) return e;
+    if ((e = b.blk.reserve(nb)) != hipSuccess) return e;
+    if ((e = b.blk_pre.reserve(nb + 1)) != hipSuccess) return e;
+    if ((e = b.bucket.reserve(cap)) != hipSuccess) return e;
+    if ((e = b.mid.reserve(cap)) != hipSuccess) return e;
+    if ((e = b.big.reserve(cap)) != hipSuccess) return e;
+    if ((e = b.ctr.reserve(1)) != hipSuccess) return e;   // last: the guard above reads it as "all of this succeeded"
     hipLaunchKernelGGL(k_vf_init, dim3(static_cast<unsigned>((tcap + 255) / 256)), dim3(256), 0, s, b.tkey, b.tslot,
                        static_cast<int>(tcap), b.ctr);
     if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -431,12 +429,6 @@ hipError_t vf_reserve(VfBuffers& b, size_t m, hipStream_t s) {
     b.tcap = tcap;
     b.n_out = &b.ctr->n_out;
     return hipSuccess;
-}
-
-void vf_free(VfBuffers& b) {
-    void* all[] = {b.tkey, b.tslot, b.sslot, b.samp, b.loc, b.blk, b.blk_pre, b.bucket, b.mid, b.big, b.ctr};
-    for (void* p : all) if (p) (void)hipFree(p);
-    b = VfBuffers{};
 }
 
 // Enqueue the filter of d_raw (n_raw AoS float3, device or pinned host memory) into d_out; the count lands in
