@@ -77,10 +77,8 @@ struct lo_ctx {
                                     //   batch's cached device KParams of this context are stale once it changes
     DevBuf<float> d_ex_terms;
     DevBuf<float> d_ex_tot;         //   large scans: the 43 sums (launch_mw_sums -> k_exact_finish)
-    DevBuf<double> d_ex_rank;       //   the iteration-0 residuals in sorted order (k_rank_sort, kExactMaxPoints), or
-                                    //   up to kExactMergeMax points: the correspondence blocks' sorted runs
+    DevBuf<double> d_ex_rank;       //   the iteration-0 residuals in sorted order (k_rank_sort, kExactMaxPoints)
     bool ex_merge = false;          //   this scan's exact scale runs in one launch (k_exact_scale_c: counting sort + sums)
-    bool ex_merge_presort = false;  //   ... or from the correspondence blocks' presorted runs (LO_EXACT_PRESORT, A/B)
     bool ex_attr = false;           //   the exact-scale kernels' dynamic-LDS attributes are set (per context)
     DevBuf<void> d_mw;              //   large scans: head records of the 43 column sums (lo_seqsum.h MwBuf)
     size_t mw_n = 0;                //   the scan size d_mw / d_mwm are laid out for (0: none)

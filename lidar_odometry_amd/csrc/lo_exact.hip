@@ -12,7 +12,6 @@
 #include <algorithm>
 #include <cfloat>
 
-#include "lo_blocksort.h"
 #include "lo_device.h"
 #include "lo_math.h"
 #include "lo_seqsum.h"
@@ -155,106 +154,11 @@ __global__ __launch_bounds__(kSeqThreads) void k_exact_scale(KParams P, const do
     if (tid == 0) st->scale = sqrt(var) / 6.0;
 }
 
-// ---- iteration 0, scans of at most kExactMergeMax points: the correspondence launch left one sorted run of 256 keys per
-// block (presort_block, lo_blocksort.h).  k_rank_runs (one workgroup per run, every run staged in LDS) places each key
-// at its rank -- its position in its own run plus, in every other run, the keys below it (later runs) or not above it
-// (earlier runs): nine probes per run, the runs' searches interleaved -- and k_exact_scale_s sums the sorted array in
-// one workgroup (mono_sum_tx: the halfway ties as two-state segment maps, a walk over ~25 binade heads). ----
-__global__ __launch_bounds__(kBlock) void k_rank_runs(KParams P, const uint64_t* __restrict__ runs, uint64_t* __restrict__ out) {
-    if (P.st->done) return;
-    if (blockIdx.x == 0) LO_XSTAMP(P.st, 15);
-    extern __shared__ uint64_t s_r[];                        // P.nb runs
-    const int nb = P.nb, b = blockIdx.x, tid = threadIdx.x;
-    {                                                        // every run's key of this lane in flight at once
-        constexpr int kRuns = kExactMergeMax / kBlock;
-        uint64_t v[kRuns];
-#pragma unroll
-        for (int r = 0; r < kRuns; ++r) v[r] = runs[(r < nb ? r : 0) * kBlock + tid];
-#pragma unroll
-        for (int r = 0; r < kRuns; ++r) if (r < nb) s_r[r * kBlock + tid] = v[r];
-    }
-    __syncthreads();
-    if (b == 0) LO_XSTAMP(P.st, 12);
-    const uint64_t x = s_r[b * kBlock + tid];
-    // equal keys: earlier runs first, then this run's order
-    const int rank = tid + (nb <= 16 ? runs_rank<16>(s_r, nb, b, x) : runs_rank<kExactMergeMax / kBlock>(s_r, nb, b, x));
-    out[rank] = x;
-    if (b == 0) LO_XSTAMP(P.st, 13);
-}
-
-template <int NT, int PT>
-__global__ __launch_bounds__(NT) void k_exact_scale_s(KParams P, const uint64_t* __restrict__ sorted) {
-    DevState* st = P.st;
-    if (st->done) return;
-    extern __shared__ double s_x[];                          // NT * PT terms
-    __shared__ MonoScratch<NT> S;
-    __shared__ int s_cnt[NT / kWave];
-    LO_XSTAMP(st, 0);
-    const int tid = threadIdx.x, base = tid * PT;
-    const int nfill = P.nb * kBlock;                         // sorted keys (finite residuals first, then +inf / NaN)
-    uint64_t v[PT];
-#pragma unroll
-    for (int q = 0; q < PT; ++q) v[q] = base + q < nfill ? sorted[base + q] : kInfKey;
-    // accepted residuals = the finite keys (a prefix); a NaN residual (accepted: the gate keeps NaN) makes the mean,
-    // the variance and the scale NaN
-    int nacc = 0;
-    bool nan = false;
-    uint64_t nan_key = 0;
-#pragma unroll
-    for (int q = 0; q < PT; ++q) {
-        nacc += v[q] < kInfKey ? 1 : 0;
-        if (v[q] > kInfKey && !nan) { nan = true; nan_key = v[q]; }
-    }
-    int cnt = 0;
-    (void)block_excl_scan_dpp<NT>(nacc, 0, [](int a, int c) { return a + c; }, s_cnt, &cnt);
-    const bool any_nan = __syncthreads_or(nan ? 1 : 0) != 0;
-    if (cnt == 0) return;                                    // too few correspondences: the PKO launch reports it
-    if (any_nan) {
-        if (nan) st->scale = sqrt(__longlong_as_double(static_cast<long long>(nan_key))) / 6.0;
-        return;
-    }
-    double x[PT];
-#pragma unroll
-    for (int q = 0; q < PT; ++q) {
-        x[q] = base + q < cnt ? __longlong_as_double(static_cast<long long>(v[q])) : 0.0;
-        s_x[base + q] = x[q];
-    }
-    __syncthreads();
-    LO_XSTAMP(st, 1);
-#ifdef LO_EXACT_STAMPS
-    unsigned long long* stp = st->dbg + 4;                  // dbg[4..6]: the mean sum's phases
-    {                                                        // diagnostic: the same sum once more from a warm
-        double warm;                                         // instruction cache (dbg[8..10] phases, dbg[11] end)
-        LO_XSTAMP(st, 7);
-        (void)mono_sum_tx<NT, PT>(x, cnt, s_x, S, warm, st->dbg + 8);
-        LO_XSTAMP(st, 11);
-    }
-#else
-    unsigned long long* stp = nullptr;
-#endif
-    double sum;
-    if (!mono_sum_tx<NT, PT>(x, cnt, s_x, S, sum, stp)) sum = chain_sum_tx<NT>(s_x, cnt, S);
-    LO_XSTAMP(st, 2);
-    LO_XSTAT(st, 14, cnt);
-    const double mean = sum / cnt;                           // std::accumulate(...) / residuals.size()
-#pragma unroll
-    for (int q = 0; q < PT; ++q) {
-        x[q] = base + q < cnt ? (x[q] - mean) * (x[q] - mean) : 0.0;
-        s_x[base + q] = x[q];                                // the walk's reads of s_x ended at mono_sum_tx's barrier
-    }
-    __syncthreads();
-    double var;
-    if (!mono_sum_tx<NT, PT>(x, cnt, s_x, S, var)) var = chain_sum_tx<NT>(s_x, cnt, S);
-    LO_XSTAMP(st, 3);
-    var /= cnt;
-    if (tid == 0) st->scale = sqrt(var) / 6.0;               // :313-315
-}
-
 // ---- iteration 0, scans of at most kExactMergeMax points, in ONE launch after the correspondence launch: the accepted
 // residuals' keys sorted by a counting sort in LDS -- bins over [min, max] of the finite keys (monotone in the key, so
 // bin order is sort order), a histogram, its scan, an atomic scatter into the bins, then each key's rank inside its
 // bin by comparing it with the bin's members (a bin holds a few keys: the bins are as many as the keys) -- and both
-// sums by mono_sum_tx.  No chip-wide pass, no presort. ----
+// sums by mono_sum_tx.  No chip-wide pass. ----
 struct KeyStat {
     uint64_t mn, mx;                                         // min / max finite key
     int cnt, nan;                                            // finite keys; NaN keys
@@ -426,7 +330,9 @@ __device__ __forceinline__ void exact_scale_c_wide(const KParams& P, int n, uint
     int* s_cnt = reinterpret_cast<int*>(s_dyn + N);
     int* s_end = s_cnt + NB;
     const int tid = threadIdx.x;
+#ifndef LO_EXACT_STAMPS
     if (tid == 0) st->dbg[23] = N;                           // the sort width this scan ran (lo_debug_counters_ex)
+#endif
     const int32_t* slot = P.slot;
     const double* res = P.kd_res ? P.kd_res : P.res_out;
     auto key_at = [&](int e) -> uint64_t {
@@ -551,6 +457,7 @@ static hipError_t scale_c_attr() {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(k_exact_scale_c<PT>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                static_cast<int>(scale_c_lds<PT>()));
 }
+// The kernels' dynamic LDS (up to 64 KB), set on the calling thread's current device (exact_prepare, per context).
 hipError_t exact_scale_c_prepare() {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_exact_scale_cd), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        static_cast<int>(std::max(kScaleWideLds, scale_c_lds<8>())));
@@ -585,35 +492,6 @@ void launch_exact_scale_c(const KParams& P, hipStream_t s) {
     else if (P.n <= 6 * kScaleC) hipLaunchKernelGGL(k_exact_scale_c<6>, dim3(1), dim3(kScaleC), scale_c_lds<6>(), s, P);
     else if (P.n <= 8 * kScaleC) hipLaunchKernelGGL(k_exact_scale_c<8>, dim3(1), dim3(kScaleC), scale_c_lds<8>(), s, P);
     else hipLaunchKernelGGL(k_exact_scale_c<16>, dim3(1), dim3(kScaleC), scale_c_lds<16>(), s, P);
-}
-
-constexpr int kScaleThreads = 256;                           // k_exact_scale_s: 4 waves, PT = padded size / 256
-template <int PT>
-static hipError_t scale_s_attr() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(k_exact_scale_s<kScaleThreads, PT>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(PT * kScaleThreads * sizeof(double)));
-}
-// The kernels' dynamic LDS (up to 64 KB), set on the calling thread's current device (exact_prepare, per context).
-hipError_t exact_scale_m_prepare() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_rank_runs), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       static_cast<int>(kExactMergeMax * sizeof(uint64_t)));
-    for (hipError_t r : {scale_s_attr<1>(), scale_s_attr<2>(), scale_s_attr<4>(), scale_s_attr<8>(), scale_s_attr<16>(),
-                         scale_s_attr<32>()})
-        if (e == hipSuccess) e = r;
-    return e;
-}
-// P.nb runs of 256 sorted keys (P.nb * 256 <= kExactMergeMax) -> sorted (P.nb * 256 keys of scratch) -> the scale
-void launch_exact_scale_m(const KParams& P, const uint64_t* runs, uint64_t* sorted, hipStream_t s) {
-    const int need = P.nb * kBlock;
-    hipLaunchKernelGGL(k_rank_runs, dim3(P.nb), dim3(kBlock), static_cast<size_t>(need) * sizeof(uint64_t), s, P, runs, sorted);
-    const size_t lds = kScaleThreads * sizeof(double);
-    constexpr int T = kScaleThreads;
-    if (need <= T) hipLaunchKernelGGL((k_exact_scale_s<T, 1>), dim3(1), dim3(T), lds, s, P, sorted);
-    else if (need <= 2 * T) hipLaunchKernelGGL((k_exact_scale_s<T, 2>), dim3(1), dim3(T), 2 * lds, s, P, sorted);
-    else if (need <= 4 * T) hipLaunchKernelGGL((k_exact_scale_s<T, 4>), dim3(1), dim3(T), 4 * lds, s, P, sorted);
-    else if (need <= 8 * T) hipLaunchKernelGGL((k_exact_scale_s<T, 8>), dim3(1), dim3(T), 8 * lds, s, P, sorted);
-    else if (need <= 16 * T) hipLaunchKernelGGL((k_exact_scale_s<T, 16>), dim3(1), dim3(T), 16 * lds, s, P, sorted);
-    else hipLaunchKernelGGL((k_exact_scale_s<T, 32>), dim3(1), dim3(T), 32 * lds, s, P, sorted);
 }
 
 // ---- iteration 0 for scans beyond the one-workgroup sort (kExactMaxPoints < n): k_exact_resid writes every point's
@@ -760,7 +638,7 @@ __global__ __launch_bounds__(kBlock) void k_exact_terms(KParams P) {
     const int s = P.slot[i];
     // term-major (long sums): the point's 14 factor rows only -- the readers form each term as the same fp32 product
     // (launch_mw_sums factored); row-major: the 43 products
-    const int nout = P.ex_ld && kExactFactored ? kExactFactors : kExactTerms;
+    const int nout = P.ex_ld ? kExactFactors : kExactTerms;
     if (s < 0) {
         for (int k = 0; k < nout; ++k) out[k * os] = 0.0f;
         return;
@@ -782,7 +660,7 @@ __global__ __launch_bounds__(kBlock) void k_exact_terms(KParams P) {
     }
     float f[14];
     exact_point_factors(P, T, scale, dl, r64, px, py, pz, sl, f);
-    if (P.ex_ld && kExactFactored) {
+    if (P.ex_ld) {
 #pragma unroll
         for (int k = 0; k < kExactFactors; ++k) out[k * os] = f[k];
         return;
@@ -866,7 +744,7 @@ __global__ __launch_bounds__(kExactSolveThreads) void k_exact_solve(KParams P, i
     if (conv) st->done = 1;
 }
 
-// ---- long columns across the chip (lo_seqsum.h "Long signed fp32 columns"): chunk sums -> classification -> walk ----
+// ---- long columns across the chip (lo_seqsum.h "Long signed fp32 columns"): classification -> compaction -> walk ----
 // The edge margin M = 2^(E - kMwEdgeBits) of a predicted binade E (lo_seqsum.h): a term whose predicted prefix lies
 // closer to an edge heads a segment, and a segment's check allows a deviation of M minus its length's half-ulps.  A
 // narrower margin trades heads for failed checks (segments summed term by term); same-box A/B on the C5 scans
@@ -932,34 +810,6 @@ template <bool FAC> struct MwCol {
     }
 };
 
-template <bool FAC>
-__global__ __launch_bounds__(256) void k_mw_chunk_sums(const float* __restrict__ col0, int ld, int n_cap,
-                                                       const int* n_dev, const DevState* st, MwBuf B) {
-    if (st && st->done) return;
-    __shared__ double s_w[2][4];
-    const int c = blockIdx.x, colI = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int n = mw_n(n_cap, n_dev), c0 = c * kMwChunk, mc = min(kMwChunk, n - c0);
-    if (mc <= 0) return;                                       // chunks past the end publish nothing
-    const MwCol<FAC> col(col0, ld, colI, c0);
-    double v = 0.0, a = 0.0;
-#pragma unroll
-    for (int k = 0; k < kMwChunk / 256; ++k) {                 // 16 terms per thread, coalesced
-        const int j = k * 256 + tid;
-        const double x = j < mc ? static_cast<double>(col[j]) : 0.0;
-        v += x;
-        a += fabs(x);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { v += __shfl_xor(v, o, 64); a += __shfl_xor(a, o, 64); }
-    if (lane == 0) { s_w[0][wid] = v; s_w[1][wid] = a; }
-    __syncthreads();
-    if (tid == 0) {
-        const size_t o = static_cast<size_t>(colI) * B.nchunks + c;
-        B.csum[o] = ((s_w[0][0] + s_w[0][1]) + s_w[0][2]) + s_w[0][3];
-        B.cabs[o] = ((s_w[1][0] + s_w[1][1]) + s_w[1][2]) + s_w[1][3];
-    }
-}
-
 constexpr int kMwWaves = kMwThreads / kWave;
 struct MwScratch {
     double wd[kMwWaves];
@@ -973,19 +823,6 @@ struct MwScratch {
     long long h_p[kMwCap];
     double h_t[kMwCap];
 };
-
-// The chunk's prediction base: the chunk sums (+ modelled drift, DRIFT) of the chunks before it, and the magnitude sum
-// through this chunk.  Every thread returns both.
-template <bool DRIFT>
-__device__ __forceinline__ void mw_base(const MwBuf& B, size_t co, int c, double* s_w, double& T0, double& A) {
-    double t0 = 0.0, a0 = 0.0;
-    for (int k = threadIdx.x; k <= c; k += kMwThreads) {
-        if (k < c) t0 += DRIFT ? B.csum[co + k] + B.dcorr[co + k] : B.csum[co + k];
-        a0 += B.cabs[co + k];
-    }
-    (void)block_excl_scan<double, kMwThreads>(t0, s_w, T0);
-    (void)block_excl_scan<double, kMwThreads>(a0, s_w, A);
-}
 
 // One thread's share of a chunk's modelled drift: each step's rounding in its predicted binade (tex: the predicted sum
 // before the thread's first term).
@@ -1002,33 +839,8 @@ __device__ __forceinline__ double mw_drift_terms(const float (&v)[kMwPT], double
     return d;
 }
 
-template <bool FAC>
-__global__ __launch_bounds__(kMwThreads) void k_mw_drift(const float* __restrict__ col0, int ld, int n_cap,
-                                                        const int* n_dev, const DevState* st, MwBuf B) {
-    if (st && st->done) return;
-    __shared__ double s_w[kMwWaves];
-    const int c = blockIdx.x, colI = blockIdx.y, tid = threadIdx.x;
-    const int n = mw_n(n_cap, n_dev), c0 = c * kMwChunk, mc = min(kMwChunk, n - c0);
-    const size_t co = static_cast<size_t>(colI) * B.nchunks;
-    if (mc <= 0) return;
-    const MwCol<FAC> col(col0, ld, colI, c0);
-    double T0, A;
-    mw_base<false>(B, co, c, s_w, T0, A);
-    const int base = tid * kMwPT;
-    float v[kMwPT];
-    col.load_run(base, mc, v);
-    double run = 0.0;
-#pragma unroll
-    for (int a = 0; a < kMwPT; ++a) run += static_cast<double>(v[a]);
-    double ttot;
-    const double tex = T0 + block_excl_scan<double, kMwThreads>(run, s_w, ttot);
-    double dtot;
-    (void)block_excl_scan<double, kMwThreads>(mw_drift_terms(v, tex), s_w, dtot);
-    if (tid == 0) B.dcorr[co + c] = dtot;
-}
-
-// Chunk values handed from one classification workgroup to the later chunks of its column inside the launch (the fused
-// path below): csum / cabs / dcorr hold kMwUnset until their chunk publishes them with an sc1 store; a reader polls
+// Chunk values handed from one classification workgroup to the later chunks of its column inside the launch (k_mw_classify
+// below): csum / cabs / dcorr hold kMwUnset until their chunk publishes them with an sc1 store; a reader polls
 // with sc1 loads (lo_device.h Mem<true>).  k_mw_compact puts kMwUnset back after the launch, mw_clear sets it at
 // allocation.  Computed values are never kMwUnset (a NaN is published as the canonical quiet NaN).  A wait is bounded
 // by kMwWaitTicks of the 100 MHz clock and then reads 0: any prediction is correct (the walk checks every head), a
@@ -1063,12 +875,10 @@ __device__ __forceinline__ void mw_block_sum2(double& x, double& y, double* s_w)
     __syncthreads();
 }
 
-// FUSED (the default): one launch computes each chunk's sums, publishes them, takes the sums of the chunks before it from
-// their workgroups (a look-back: every workgroup waits only for lower chunks of its own column, dispatched before it),
-// then its modelled drift the same way, then classifies -- k_mw_chunk_sums and k_mw_drift fold in.  The prediction
-// base is the same quantity summed in another order (T0 = chunk sums + drift corrections of the chunks before).
-// !FUSED: the three-launch path (LO_MW_SPLIT=1, A/B).
-template <bool FUSED, bool FAC>
+// One launch computes each chunk's sums, publishes them, takes the sums of the chunks before it from their workgroups
+// (a look-back: every workgroup waits only for lower chunks of its own column, dispatched before it), then its modelled
+// drift the same way, then classifies.  The prediction base is T0 = chunk sums + drift corrections of the chunks before.
+template <bool FAC>
 __global__ __launch_bounds__(kMwThreads, 4) void k_mw_classify(const float* __restrict__ col0, int ld, int n_cap,
                                                              const int* n_dev, const DevState* st, MwBuf B) {
     if (st && st->done) return;
@@ -1087,29 +897,24 @@ __global__ __launch_bounds__(kMwThreads, 4) void k_mw_classify(const float* __re
     double run = 0.0;
 #pragma unroll
     for (int a = 0; a < kMwPT; ++a) run += static_cast<double>(v[a]);
-    double T0, A, ttot, ex;
-    if constexpr (FUSED) {
-        ex = block_excl_scan<double, kMwThreads>(run, S.wd, ttot);
-        double ab = 0.0, unused = 0.0;
+    double ttot;
+    const double ex = block_excl_scan<double, kMwThreads>(run, S.wd, ttot);
+    double ab = 0.0, unused = 0.0;
 #pragma unroll
-        for (int a = 0; a < kMwPT; ++a) ab += fabs(static_cast<double>(v[a]));
-        mw_block_sum2(ab, unused, S.wd2);
-        if (tid == 0) { mw_publish(B.csum + co + c, ttot); mw_publish(B.cabs + co + c, ab); }
-        double t0 = 0.0, a0 = 0.0;
-        for (int k = tid; k < c; k += kMwThreads) { t0 += mw_await(B.csum + co + k); a0 += mw_await(B.cabs + co + k); }
-        mw_block_sum2(t0, a0, S.wd2);
-        A = a0 + ab;
-        double d = mw_drift_terms(v, t0 + ex), dp = 0.0;
-        mw_block_sum2(d, dp, S.wd2);
-        if (tid == 0) mw_publish(B.dcorr + co + c, d);
-        for (int k = tid; k < c; k += kMwThreads) dp += mw_await(B.dcorr + co + k);
-        double unused2 = 0.0;
-        mw_block_sum2(dp, unused2, S.wd2);
-        T0 = t0 + dp;
-    } else {
-        mw_base<true>(B, co, c, S.wd, T0, A);
-        ex = block_excl_scan<double, kMwThreads>(run, S.wd, ttot);
-    }
+    for (int a = 0; a < kMwPT; ++a) ab += fabs(static_cast<double>(v[a]));
+    mw_block_sum2(ab, unused, S.wd2);
+    if (tid == 0) { mw_publish(B.csum + co + c, ttot); mw_publish(B.cabs + co + c, ab); }
+    double t0 = 0.0, a0 = 0.0;
+    for (int k = tid; k < c; k += kMwThreads) { t0 += mw_await(B.csum + co + k); a0 += mw_await(B.cabs + co + k); }
+    mw_block_sum2(t0, a0, S.wd2);
+    const double A = a0 + ab;
+    double d = mw_drift_terms(v, t0 + ex), dp = 0.0;
+    mw_block_sum2(d, dp, S.wd2);
+    if (tid == 0) mw_publish(B.dcorr + co + c, d);
+    for (int k = tid; k < c; k += kMwThreads) dp += mw_await(B.dcorr + co + k);
+    double unused2 = 0.0;
+    mw_block_sum2(dp, unused2, S.wd2);
+    const double T0 = t0 + dp;
     const double eps_t = ldexp(A + fabs(T0), -45);             // bound on the in-chunk prediction error (see above)
     const double tex = T0 + ex;
     {
@@ -1492,17 +1297,8 @@ template <bool FAC>
 static void launch_mw_sums_t(const float* col0, int ld, int ncol, int n_cap, const int* n_dev, const DevState* st,
                              const MwBuf& B, float* out, long long* stats, hipStream_t s) {
     const int nc = (n_cap + kMwChunk - 1) / kMwChunk;
-    static const bool split = std::getenv("LO_MW_SPLIT") != nullptr;   // A/B: the three-launch classification
     if (nc > 0) {
-        if (split) {
-            hipLaunchKernelGGL(k_mw_chunk_sums<FAC>, dim3(nc, ncol), dim3(256), 0, s, col0, ld, n_cap, n_dev, st, B);
-            hipLaunchKernelGGL(k_mw_drift<FAC>, dim3(nc, ncol), dim3(kMwThreads), 0, s, col0, ld, n_cap, n_dev, st, B);
-            hipLaunchKernelGGL((k_mw_classify<false, FAC>), dim3(nc, ncol), dim3(kMwThreads), 0, s, col0, ld, n_cap, n_dev,
-                               st, B);
-        } else {
-            hipLaunchKernelGGL((k_mw_classify<true, FAC>), dim3(nc, ncol), dim3(kMwThreads), 0, s, col0, ld, n_cap, n_dev,
-                               st, B);
-        }
+        hipLaunchKernelGGL(k_mw_classify<FAC>, dim3(nc, ncol), dim3(kMwThreads), 0, s, col0, ld, n_cap, n_dev, st, B);
         hipLaunchKernelGGL(k_mw_compact, dim3(nc, ncol), dim3(256), 0, s, n_cap, n_dev, st, B);
     }
     hipLaunchKernelGGL(k_mw_walk<FAC>, dim3(ncol), dim3(64), 0, s, col0, ld, n_cap, n_dev, st, B, out, stats);

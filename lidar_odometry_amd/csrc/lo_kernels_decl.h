@@ -53,19 +53,14 @@ __global__ void k_surfel_fit(const FitJob* jobs, const float* cs, int n, float t
                              FitOut* out);
 void launch_exact_scale(const KParams& P, int n, double* sorted, hipStream_t s);
 hipError_t exact_scale_rank_prepare();
-hipError_t exact_scale_m_prepare();
 hipError_t exact_scale_c_prepare();
 void launch_exact_scale_c(const KParams& P, hipStream_t s);
-void launch_exact_scale_m(const KParams& P, const uint64_t* runs, uint64_t* sorted, hipStream_t s);
 void launch_seq_sum_diag(const double* x, int n, double* sort, double* out, long long* stats, hipStream_t s);
 void launch_mw_sums(const float* col0, int ld, int ncol, int n_cap, const int* n_dev, const DevState* st, const MwBuf& B,
                     float* out, long long* stats, hipStream_t s, bool factored);
 size_t mw_bytes(int ncol, int n_cap);
 MwBuf mw_layout(void* mem, int ncol, int n_cap);
 hipError_t mw_clear(const MwBuf& B, int ncol, hipStream_t s);
-#ifndef LO_EXACT_FACTORED
-#define LO_EXACT_FACTORED 1                                  // lo_exact.h kExactFactored
-#endif
 void launch_mwm_scale(KParams P, const double* sorted, const MwmBuf& B, hipStream_t s);
 size_t mwm_bytes(int n_cap);
 MwmBuf mwm_layout(void* mem, int n_cap);

@@ -139,8 +139,6 @@ static void launch_pick_knn(lo_ctx* c, const KParams& P, int it) {
     hipLaunchKernelGGL(k_plane, dim3(P.nb), blk, 0, c->stream, P, 0);
 }
 
-static_assert(kExactMaxPoints >= 2 * kExactMergeMax, "d_ex_rank holds the presorted runs and the merged keys");
-
 // A scan's first correspondence launch, bracketed by HIP events on the context stream when stage timing is on
 // (the kernel's in-step duration, as opposed to lo_bench_kernel's back-to-back launches).
 static void launch_correspond_first(lo_ctx* c, const KParams& P0, bool kd, int with_stats = 1) {
@@ -162,26 +160,23 @@ static void launch_correspond_first(lo_ctx* c, const KParams& P0, bool kd, int w
 // write their residuals out, sort them with hipCUB's radix sort and sum them across the chip (launch_mwm_scale).
 static int exact_prepare(lo_ctx* c, KParams& P, size_t n, int* n2) {
     // the term buffer: row-major [point][43] up to kExactMaxPoints (k_exact_terms + k_exact_solve), term-major rows of
-    // round_up(n, 64) beyond (the 14 factor rows, or the 43 term columns in the LO_EXACT_FACTORED=0 A/B build)
+    // round_up(n, 64) beyond (the 14 factor rows)
     const size_t ex_need = std::max(static_cast<size_t>(kExactMaxPoints) * kExactTerms,
-                                    (kExactFactored ? kExactFactors : kExactTerms) * ((n + 63) & ~static_cast<size_t>(63)));
+                                    kExactFactors * ((n + 63) & ~static_cast<size_t>(63)));
     LO_HIP(c, c->d_ex_terms.reserve(ex_need));
     LO_HIP(c, c->d_ex_rank.reserve(kExactMaxPoints));
     if (!c->ex_attr) {
         LO_HIP(c, exact_scale_rank_prepare());
-        LO_HIP(c, exact_scale_m_prepare());
         LO_HIP(c, exact_scale_c_prepare());
         c->ex_attr = true;
     }
     P.ex_terms = c->d_ex_terms;
     P.scale_given = 1;
-    // up to kExactMergeMax points the iteration-0 correspondence launch presorts its blocks (P0.presort, set by the
-    // caller from ex_merge) and one workgroup merges and sums them
-    // (r06: up to kExactMaxPoints; a device-counted scan -- the voxel filter's output -- picks its sort width from the
-    // count on the device, k_exact_scale_cd, instead of sizing the sort by the bound ceil(n_raw / stride))
+    // up to kExactMaxPoints points one workgroup sorts and sums the iteration-0 residuals (a device-counted scan -- the
+    // voxel filter's output -- picks its sort width from the count on the device, k_exact_scale_cd, instead of sizing
+    // the sort by the bound ceil(n_raw / stride))
     c->ex_merge = n <= static_cast<size_t>(kExactMaxPoints);
-    c->ex_merge_presort = n <= static_cast<size_t>(kExactMergeMax) && std::getenv("LO_EXACT_PRESORT") != nullptr;   // A/B
-    if (std::getenv("LO_EXACT_RANKSORT")) c->ex_merge = c->ex_merge_presort = false;   // A/B: the chip-wide rank sort
+    if (std::getenv("LO_EXACT_RANKSORT")) c->ex_merge = false;   // A/B: the chip-wide rank sort
     if (n > static_cast<size_t>(kExactMaxPoints)) {
         LO_HIP(c, c->d_ex_tot.reserve(64));
         if (c->mw_n < n) {                                   // the column sums' head records
@@ -217,20 +212,15 @@ static int exact_prepare(lo_ctx* c, KParams& P, size_t n, int* n2) {
 }
 // the iteration-0 scale of reference-exact mode (between the scan's first correspondence launch and its first PKO)
 static void launch_exact_scale_any(lo_ctx* c, const KParams& P, int n2, hipStream_t s) {
-    if (c->ex_merge && !c->ex_merge_presort) {
+    if (c->ex_merge) {
         launch_exact_scale_c(P, s);                          // counting sort + sums in one workgroup (<= 16384 points)
         return;
     }
-    if (c->ex_merge) {
-        // runs in the first half of d_ex_rank, the sorted keys in the second (kExactMaxPoints = 2 kExactMergeMax)
-        launch_exact_scale_m(P, reinterpret_cast<const uint64_t*>(c->d_ex_rank.get()),
-                             reinterpret_cast<uint64_t*>(c->d_ex_rank.get()) + kExactMergeMax, s);
-        return;
-    }
     if (n2 > 0) {
-        launch_exact_scale(P, n2, c->d_ex_rank, s);
+        launch_exact_scale(P, n2, c->d_ex_rank, s);          // rank sort across the chip (A/B and diagnostics)
         return;
     }
+    // beyond kExactMaxPoints: hipCUB sort + long mono sums
     const int n = P.n;                                       // the bound (a device-filtered scan counts on the device)
     hipLaunchKernelGGL(k_exact_resid, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, P, c->d_ex_res);
     size_t tmp = c->d_ex_sort_tmp.capacity();
@@ -245,7 +235,7 @@ static void launch_exact_iteration(lo_ctx* c, const KParams& P, const KParams& P
     launch_pko(c, P, it);
     hipLaunchKernelGGL(k_exact_terms, dim3(P.nb), dim3(kBlock), 0, c->stream, P);
     if (P.ex_ld) {                                           // large scan: 43 parallel sequential-sum reproductions
-        launch_mw_sums(P.ex_terms, P.ex_ld, 43, P.n, P.n_dev, P.st, c->mw, P.ex_tot, nullptr, c->stream, LO_EXACT_FACTORED != 0);
+        launch_mw_sums(P.ex_terms, P.ex_ld, 43, P.n, P.n_dev, P.st, c->mw, P.ex_tot, nullptr, c->stream, true);
         hipLaunchKernelGGL(k_exact_finish, dim3(1), dim3(64), 0, c->stream, P, it);
     } else {
         hipLaunchKernelGGL(k_exact_solve, dim3(1), dim3(512), 0, c->stream, P, it);   // kExactSolveThreads
@@ -285,7 +275,6 @@ int enqueue_optimize(lo_ctx* c, const float* d_pts, size_t n, const float T_init
             if (rc3 != LO_OK) return rc3;
             P0.ex_terms = P.ex_terms;
             P0.scale_given = P.scale_given;
-            if (c->ex_merge_presort) P0.presort = reinterpret_cast<uint64_t*>(c->d_ex_rank.get());
             if (!(fused && P.cand_rec && n2 > 0)) {
                 // reference-exact GN loop without candidates (lo_exact.hip): correspondences, (iteration 0) sorted-order
                 // scale, PKO, per-point fp32 terms, sequential sums + fp32 LDLT + SVD-projected update
@@ -522,7 +511,6 @@ retry:
     if (c->exact && (rc = exact_prepare(c, P, n_curr, &n2)) != LO_OK) return rc;
     KParams P0 = P;
     P0.init = 1;
-    if (c->exact && c->ex_merge_presort) P0.presort = reinterpret_cast<uint64_t*>(c->d_ex_rank.get());
     std::memcpy(P0.T0, T_curr, sizeof(float) * 12);
     // small clouds with PKO: the odometry path's launch sequence (candidates solved in the PKO launch, k_pick_knn
     // taking the selected one fused with the next kNN search); reference-exact mode as there

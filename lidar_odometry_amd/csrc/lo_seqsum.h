@@ -376,7 +376,9 @@ __device__ __forceinline__ T block_excl_scan_dpp(T v, T ident, Op op, T* s_w, T*
 
 constexpr int kTxHeadCap = 256;                    // heads per sum (more: the plain chain)
 constexpr int kTxAny = 100000;                     // walk record: a head without a segment (every check passes)
-constexpr int kExactMergeMax = 8192;               // exact scale from presorted runs (k_rank_runs + k_exact_scale_s)
+constexpr int kExactMergeMax = 8192;               // lock-step limit of the batched exact scale: jobs up to this size share
+                                                   //   one k_exact_scale_cb launch (lo_batch.hip); larger ones run singly
+constexpr uint64_t kInfKey = 0x7FF0000000000000ull;   // exact scale sort key of +inf: no correspondence / past the scan
 template <int NT>
 struct MonoScratch {
     double wd[NT / kWave];
@@ -633,37 +635,6 @@ __device__ __forceinline__ bool mono_sum_tx(const double (&x)[PT], int cnt, cons
     return true;
 }
 
-// Sorting support for the exact scale (k_rank_runs): the number of keys of a sorted 256-key run below x (STRICT) or
-// not above x, for every run at once (the runs' nine-probe binary searches interleaved: NR loads in flight per probe).
-template <int NR>
-__device__ __forceinline__ int runs_rank(const uint64_t* s_r, int nb, int b, uint64_t x) {
-    int p[NR];
-    bool use[NR], le[NR];
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        p[r] = (r < nb ? r : 0) * 256;                     // a row past nb reads row 0 and is not counted
-        use[r] = r < nb && r != b;
-        le[r] = r < b;                                     // earlier runs: keys not above x; later runs: below x
-    }
-#pragma unroll
-    for (int st = 128; st >= 1; st >>= 1) {
-        uint64_t v[NR];
-#pragma unroll
-        for (int r = 0; r < NR; ++r) v[r] = s_r[p[r] + st - 1];
-#pragma unroll
-        for (int r = 0; r < NR; ++r) p[r] += (le[r] ? v[r] <= x : v[r] < x) ? st : 0;
-    }
-    int rank = 0;
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        const uint64_t v = s_r[p[r]];
-        const int c = (p[r] & 255) + ((le[r] ? v <= x : v < x) ? 1 : 0);
-        rank += use[r] ? c : 0;
-    }
-    return rank;
-}
-
-
 }  // namespace lo
 
 namespace lo {
@@ -690,16 +661,18 @@ namespace lo {
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Long signed fp32 columns across the chip (the exact mode's 43 normal-equation sums of scans beyond kExactMaxPoints,
-// up to 4M terms each).  The exact running sum is unknown until the walk reaches a term, so the phases run as
-// launches over every 4096-term chunk of every column at once:
-//   1. k_mw_chunk_sums: each chunk's fp64 sum and sum of magnitudes;
-//   2. k_mw_drift:      each chunk's modelled rounding error: the fp32 running sum drifts from the exact prefix by the
-//      sum of its step roundings, rint(x / u) u - x with u from the predicted binade -- over a long column of shrinking
-//      sums the drift outgrows the checks' margin, so the prediction carries it;
-//   3. k_mw_classify:   each chunk's prediction base T0 = the fp64 sum of the chunks before it plus their modelled drift,
-//      its heads and integer prefix, and for every head the record the walk needs (its term, the segment's sum u * Q,
-//      the check's interval) -- in HBM; k_mw_compact then lays the records out in walk order;
-//   4. k_mw_walk:       one wave per column walks every head in order, 64 at a time as a plain fp32 chain (operands
+// up to 4M terms each).  The exact running sum is unknown until the walk reaches a term, so every 4096-term chunk of
+// every column predicts it:
+//   1. k_mw_classify, one workgroup per chunk, one launch: the chunk's fp64 sum and sum of magnitudes, published to the
+//      later chunks of its column; the sums of the chunks before it, taken from their workgroups inside the launch (a
+//      look-back: a workgroup waits only for lower chunks of its own column, dispatched before it, each wait bounded);
+//      the chunk's modelled rounding error, handed on the same way -- the fp32 running sum drifts from the exact prefix
+//      by the sum of its step roundings, rint(x / u) u - x with u from the predicted binade, and over a long column of
+//      shrinking sums the drift outgrows the checks' margin, so the prediction carries it; then, from the prediction
+//      base T0 = the fp64 sum of the chunks before plus their modelled drift, the chunk's heads and integer prefix, and
+//      for every head the record the walk needs (its term, the segment's sum u * Q, the check's interval) -- in HBM;
+//   2. k_mw_compact lays the records out in walk order and resets the values handed between the chunks;
+//   3. k_mw_walk: one wave per column walks every head in order, 64 at a time as a plain fp32 chain (operands
 //      broadcast from LDS, the next window's records in flight), then checks the 64 heads lane-parallel; from a failed
 //      check on, head by head, a failed segment term by term.
 // The prediction error bound eps_t is 2^-45 times (the column's sum of magnitudes up to the chunk's end + |T0|): only

@@ -7,7 +7,7 @@ import sys
 
 def main():
     db = sys.argv[1]
-    marker = sys.argv[2] if len(sys.argv) > 2 else "k_rank_runs"
+    marker = sys.argv[2] if len(sys.argv) > 2 else "k_exact_scale_c"
     which = [int(v) for v in sys.argv[3].split(",")] if len(sys.argv) > 3 else [300, 301]
     c = sqlite3.connect(db)
     rows = c.execute("select name, start, end, queue_id from kernels where name like '%lo::k_%' order by start").fetchall()
