@@ -58,6 +58,11 @@ int lo_gmap_add_keyframe(lo_gmap* g, int64_t keyframe_id, const float* pts_xyz, 
  * feature cloud), copied device to device; only its 4-byte count is read back.  LO_ERR_STATE when the context has no
  * such scan. */
 int lo_gmap_add_from_scan(lo_gmap* g, int64_t keyframe_id);
+/* Keyframe `index` (insertion order) in place: its id (nullable), the device pointer of its stored cloud inside the
+ * arena (sensor frame, AoS float3) and its point count -- no copy, e.g. the matched cloud of lo_icp_optimize_loop_dev.
+ * The pointer is valid until lo_gmap_clear or lo_gmap_destroy (the arena never moves).  A keyframe stored with 0
+ * points gives n = 0 (its pointer is then not to be read).  LO_ERR_ARG for an index past the end. */
+int lo_gmap_keyframe_points(lo_gmap* g, size_t index, int64_t* keyframe_id, const float** d_xyz, size_t* n);
 
 /* The map at the given poses: poses_3x4 is n_poses row-major 3x4 world-from-sensor matrices, one per keyframe in
  * insertion order; n_poses must equal lo_gmap_keyframes (else LO_ERR_ARG).  voxel_size > 0: the voxel-grid filter of

@@ -305,6 +305,23 @@ long long lo_voxel_filter_gpu(lo_ctx* ctx, const float* raw_xyz, size_t n_raw, f
 int lo_icp_optimize_loop(lo_ctx* ctx, const float* curr_xyz, size_t n_curr, const float T_curr[12],
                          const float* matched_xyz, size_t n_matched, const float T_matched[12],
                          float T_rel_out[12], float* inlier_ratio, lo_iter_log* logs, lo_stats* stats);
+/* The same contract on device-resident clouds: d_curr / d_matched are device pointers (AoS float3) on the context's
+ * device, e.g. the context's filtered scan and a keyframe inside an lo_gmap arena (lo_gmap_keyframe_points).  The
+ * matched cloud is put in the world on the device (transform_point_cloud's fp32 order, each operation separately
+ * rounded) and its grid is built there (the device builder behind lo_devmap_sync_points, with the loop path's cell
+ * occupancy rule); up to 8192 matched points take the all-pairs search, filled by device-to-device copies.  The current
+ * cloud is copied into the context's scan buffer, or used in place when it already is that buffer (any other overlap
+ * with it is not allowed).  Everything after the grid is lo_icp_optimize_loop's own code, so for equal inputs the
+ * return code, T_rel_out, inlier_ratio, logs and stats (gpu_ms aside) are bit-identical to it.  A solve that meets a
+ * deciding distance tie brings the gridded points down once, builds the kd visit order on the host and runs again,
+ * as lo_icp_result does for a device-built odometry grid.  Both clouds must stay valid and unchanged until the call
+ * returns.  n_curr > max_points: LO_ERR_CAPACITY; a non-finite matched world point: LO_ERR_ARG. */
+int lo_icp_optimize_loop_dev(lo_ctx* ctx, const float* d_curr, size_t n_curr, const float T_curr[12],
+                             const float* d_matched, size_t n_matched, const float T_matched[12],
+                             float T_rel_out[12], float* inlier_ratio, lo_iter_log* logs, lo_stats* stats);
+/* Loop-closure solves (either entry point) of this context that were run again with the kd visit order because a
+ * distance tie decided a query's five neighbours or their order. */
+long long lo_loop_reruns(const lo_ctx* ctx);
 
 /* find_correspondences (IterativeClosestPointOptimizer.cpp:587-645) at pose T:
  * per-point valid flag and fp64 residual |n.(p_w - c)| (0 where invalid). Returns the count. */

@@ -1,7 +1,7 @@
 /* lo_odometry.h — the frame loop around the ICP step (the hot path's caller), MI355X device path.
  *
- * Replaces Estimator::process_frame (src/processing/Estimator.cpp:115-233) for odometry without loop
- * closure / PGO (out of scope, off in all parity runs):
+ * Replaces Estimator::process_frame (src/processing/Estimator.cpp:115-233).  Loop closure / PGO is opt-in
+ * (lo_odom_enable_loop_closure, below) and off in all odometry parity runs; without it the loop is:
  *   preprocess_frame (:561-589)            -> device FastVoxelFilter (lo_icp_optimize_raw)
  *   first frame (:235-269)                 -> pose = initial pose, create_keyframe
  *   guess = prev_pose * velocity (:154)    -> SE3f product with SO3 re-projection (MathUtils.h:144-147)
@@ -20,6 +20,7 @@
 #include <stddef.h>
 
 #include "lo_icp.h"
+#include "lo_iris.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -69,6 +70,82 @@ int           lo_odom_process(lo_odometry* o, const float* raw_xyz, size_t n, fl
 int           lo_odom_flush(lo_odometry* o);
 size_t        lo_odom_keyframe_count(const lo_odometry* o);
 size_t        lo_odom_map_surfels(const lo_odometry* o);
+
+/* ---- loop closure in the frame loop (opt-in) ----
+ * The reference's SLAM back end around the frame loop: create_keyframe's loop bookkeeping (Estimator.cpp:370-530),
+ * run_pgo_for_loop (:959-1137) and apply_pending_pgo_result_if_available (:1139-1194), joined from the library's own
+ * pieces: lo_iris (candidates), lo_icp_optimize_loop_dev (verification, on the keyframe clouds where they already
+ * are: the context's filtered scan and the lo_gmap arena), lo_pgo (the graph), lo_devmap_apply_transform (the map)
+ * and lo_gmap (the corrected global map).
+ *
+ * At every keyframe, after the map update: the feature cloud is stored (lo_gmap_add_from_scan), the pose graph is
+ * extended (first keyframe: prior; later: odometry factor with relative = prev_keyframe_pose^-1 * pose, SE3f algebra,
+ * the previous keyframe's CURRENT pose), and when keyframe_id - last_successful_loop_keyframe >= cooldown_keyframes
+ * (that counter starts at -1, Estimator.cpp:38) the detector is queried with the device scan, THEN the keyframe is
+ * added to it.  The reference adds first and queries afterwards; the order is equivalent because a database entry
+ * closer than min_keyframe_gap ids -- the keyframe itself included -- is skipped by the selection, for every
+ * min_keyframe_gap >= 1 (lo_odom_enable_loop_closure refuses smaller values).
+ * A candidate is verified by the loop ICP at the two keyframes' current poses and accepted when it returns LO_OK and
+ * inlier_ratio >= min_inlier_ratio.  Then T_corrected = T_curr * T_rel, constraint = T_matched^-1 * T_corrected,
+ * lo_pgo_add_loop_and_optimize(matched, curr, constraint).  On PGO success every keyframe takes its optimized pose;
+ * correction = after * before^-1 of the last keyframe moves the map (lo_devmap_apply_transform, then
+ * lo_devmap_sync_points in KDTree mode; LO_HOST_MAP=1: lo_voxelmap_apply_transform + lo_map_sync_voxelmap); the
+ * previous-frame pose behind the next guess becomes the keyframe's optimized pose (the reference's m_previous_frame
+ * IS that keyframe); the stored velocity is kept; the cooldown counter becomes this keyframe's id.
+ * The pose should_create_keyframe compares against does NOT move: the reference keeps it as a copy
+ * (m_last_keyframe_pose, set at Estimator.cpp:494, read at :356-359) that apply_pending_pgo_result_if_available
+ * never touches, so the next keyframe test still measures from the uncorrected keyframe pose.
+ *
+ * Synchronous by design.  The reference runs detection, loop ICP and PGO on a background thread and applies the
+ * result at the start of the first process_frame after the thread finished, so the frame at which a correction lands
+ * depends on wall-clock time.  Here everything runs inside the keyframe's own lo_odom_process call and lands before
+ * the next frame is tracked -- what the reference does when its thread finishes between two frames.  Runs are
+ * therefore reproducible.
+ *
+ * Without lo_odom_enable_loop_closure the frame loop does exactly what it did: no allocation, launch or sync more. */
+typedef struct lo_loop_config {      /* defaults: ConfigUtils.h:117-134 */
+    lo_iris_config iris;             /* 0.3f, 50, 10.0f */
+    int    cooldown_keyframes;       /* loop_min_keyframe_gap's second use (kitti.yaml:70): 50 */
+    float  min_inlier_ratio;         /* 0.3f (Estimator.cpp:1015) */
+    double odom_trans_noise, odom_rot_noise, loop_trans_noise, loop_rot_noise;   /* 0.5, 0.5, 1.0, 1.0 */
+    size_t max_keyframes;            /* iris database + gmap keyframes (default 4096) */
+    size_t max_points;               /* gmap arena, points over all keyframes (default 2^22) */
+} lo_loop_config;
+
+/* The last keyframe's loop attempt. */
+typedef struct lo_loop_event {
+    int    keyframe_id;              /* the keyframe (-1: no keyframe yet) */
+    int    queried;                  /* 1: the detector was queried; 0: cooled down */
+    int    candidate_id;             /* matched keyframe id, -1: none */
+    float  candidate_distance;       /* its iris distance and bias (0 / 0 without a candidate) */
+    int    candidate_bias;
+    int    icp_status;               /* lo_icp_optimize_loop_dev's return (meaningful with a candidate only) */
+    int    icp_iterations;
+    float  inlier_ratio;
+    int    accepted;                 /* 1: verified, PGO succeeded, poses and map corrected */
+    int    pgo_converged;
+    int    pgo_iterations;
+    float  correction_translation;   /* |t| of the last keyframe's correction, m */
+    float  correction_angle;         /* |Log(R)| of it, rad */
+    double detect_ms, icp_ms, pgo_ms, map_ms;   /* host wall time of the four stages */
+} lo_loop_event;
+
+void      lo_loop_config_default(lo_loop_config* cfg);
+/* Creates the detector, the keyframe store and the pose graph.  Before the first frame, else LO_ERR_STATE (also when
+ * already enabled); LO_ERR_ARG for a null pointer, iris.min_keyframe_gap < 1 or a zero capacity. */
+int       lo_odom_enable_loop_closure(lo_odometry* o, const lo_loop_config* cfg);
+/* LO_ERR_STATE when loop closure is not enabled.  A keyframe that exceeds max_keyframes or max_points makes its
+ * lo_odom_process return LO_ERR_CAPACITY (text in lo_odom_last_error). */
+int       lo_odom_last_loop(const lo_odometry* o, lo_loop_event* out);
+size_t    lo_odom_loop_count(const lo_odometry* o);          /* loops closed */
+/* The keyframes' current (corrected) poses in keyframe order; ids / poses_3x4 nullable; returns the keyframe count
+ * (at most cap entries are written).  0 when loop closure is not enabled. */
+size_t    lo_odom_keyframe_poses(const lo_odometry* o, int* ids, float* poses_3x4, size_t cap);
+/* lo_gmap_build of the stored keyframe clouds at those poses; then lo_gmap_download / lo_gmap_save_ply of it
+ * (Estimator::save_map_to_ply, Estimator.cpp:1248-1305).  LO_ERR_STATE when loop closure is not enabled. */
+int       lo_odom_build_map(lo_odometry* o, float voxel_size, size_t* out_n);
+long long lo_odom_map_points(lo_odometry* o, float* out_xyz, size_t cap);
+int       lo_odom_save_map_ply(lo_odometry* o, const char* path, float voxel_size);
 
 #ifdef __cplusplus
 }

@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = (
     "lo_config_default_kitti", "lo_config_default_mid360", "lo_pko_kernel_from_name", "lo_create", "lo_destroy", "lo_last_error",
     "lo_device", "lo_get_config", "lo_map_set_surfels", "lo_map_surfel_count", "lo_map_set_points",
     "lo_map_point_count", "lo_icp_optimize", "lo_icp_optimize_raw_async", "lo_icp_optimize_raw", "lo_filtered_points",
-    "lo_voxel_filter_gpu", "lo_icp_optimize_async", "lo_icp_optimize_loop", "lo_host_alloc", "lo_host_free",
+    "lo_voxel_filter_gpu", "lo_icp_optimize_async", "lo_icp_optimize_loop", "lo_icp_optimize_loop_dev", "lo_loop_reruns", "lo_host_alloc", "lo_host_free",
     "lo_icp_result", "lo_sync", "lo_stream", "lo_set_stream", "lo_set_exact", "lo_set_pipeline", "lo_pipeline_status", "lo_set_pko_groups", "lo_update_config", "lo_map_sync_surfels", "lo_set_stage_timing", "lo_stage_time", "lo_pko_em_stats", "lo_icp_export_pose", "lo_bench_kernel", "lo_bench_correspond_rr", "lo_find_correspondences", "lo_knn_search", "lo_pko_scale_factor",
     "lo_build_normal_equations", "lo_pko_sample_indices", "lo_pko_sample_indices_host", "lo_debug_counters", "lo_debug_counters_ex", "lo_debug_live_bytes", "lo_stage_span", "lo_seq_sum_f64", "lo_seq_sum_f32",
     "lo_batch_create", "lo_batch_destroy", "lo_batch_last_error", "lo_batch_size", "lo_batch_optimize_async",
@@ -42,6 +42,8 @@ EXPORTED_SYMBOLS = (
     # include/lo_odometry.h
     "lo_odom_config_default_kitti", "lo_odom_create", "lo_odom_destroy", "lo_odom_last_error", "lo_odom_set_initial_pose",
     "lo_odom_process", "lo_odom_keyframe_count", "lo_odom_map_surfels", "lo_odom_set_exact", "lo_odom_flush",
+    "lo_loop_config_default", "lo_odom_enable_loop_closure", "lo_odom_last_loop", "lo_odom_loop_count",
+    "lo_odom_keyframe_poses", "lo_odom_build_map", "lo_odom_map_points", "lo_odom_save_map_ply",
     # include/lo_io.h
     "lo_load_kitti_bin", "lo_load_ply", "lo_kitti_pose_line", "lo_save_trajectory_kitti", "lo_save_ply",
     # include/lo_pgo.h
@@ -55,7 +57,7 @@ EXPORTED_SYMBOLS = (
     # include/lo_gmap.h
     "lo_gmap_create", "lo_gmap_destroy", "lo_gmap_last_error", "lo_gmap_clear", "lo_gmap_keyframes", "lo_gmap_points",
     "lo_gmap_add_keyframe", "lo_gmap_add_from_scan", "lo_gmap_build", "lo_gmap_download", "lo_gmap_device_points",
-    "lo_gmap_save_ply", "lo_gmap_bench_build", "lo_gmap_stage_ms", "lo_gmap_voxelgrid_host",
+    "lo_gmap_save_ply", "lo_gmap_bench_build", "lo_gmap_stage_ms", "lo_gmap_voxelgrid_host", "lo_gmap_keyframe_points",
 )
 LO_GMAP_STAGES = 4
 
@@ -106,6 +108,21 @@ class LoIrisCandidate(C.Structure):
                 ("bias", C.c_int)]
 
 
+class LoLoopConfig(C.Structure):
+    _fields_ = [("iris", LoIrisConfig), ("cooldown_keyframes", C.c_int), ("min_inlier_ratio", C.c_float),
+                ("odom_trans_noise", C.c_double), ("odom_rot_noise", C.c_double), ("loop_trans_noise", C.c_double),
+                ("loop_rot_noise", C.c_double), ("max_keyframes", C.c_size_t), ("max_points", C.c_size_t)]
+
+
+class LoLoopEvent(C.Structure):
+    _fields_ = [("keyframe_id", C.c_int), ("queried", C.c_int), ("candidate_id", C.c_int),
+                ("candidate_distance", C.c_float), ("candidate_bias", C.c_int), ("icp_status", C.c_int),
+                ("icp_iterations", C.c_int), ("inlier_ratio", C.c_float), ("accepted", C.c_int),
+                ("pgo_converged", C.c_int), ("pgo_iterations", C.c_int), ("correction_translation", C.c_float),
+                ("correction_angle", C.c_float), ("detect_ms", C.c_double), ("icp_ms", C.c_double),
+                ("pgo_ms", C.c_double), ("map_ms", C.c_double)]
+
+
 _lib = None
 
 
@@ -147,6 +164,11 @@ def lib():
     L.lo_icp_optimize_loop.restype = C.c_int
     L.lo_icp_optimize_loop.argtypes = [vp, fp, C.c_size_t, fp, fp, C.c_size_t, fp, fp, fp, C.POINTER(LoIterLog),
                                        C.POINTER(LoStats)]
+    L.lo_icp_optimize_loop_dev.restype = C.c_int
+    L.lo_icp_optimize_loop_dev.argtypes = [vp, vp, C.c_size_t, fp, vp, C.c_size_t, fp, fp, fp, C.POINTER(LoIterLog),
+                                           C.POINTER(LoStats)]
+    L.lo_loop_reruns.restype = C.c_longlong
+    L.lo_loop_reruns.argtypes = [vp]
     L.lo_filtered_points.restype = C.c_longlong
     L.lo_filtered_points.argtypes = [vp, fp, C.c_size_t]
     L.lo_voxel_filter_gpu.restype = C.c_longlong
@@ -167,6 +189,18 @@ def lib():
     L.lo_odom_set_exact.argtypes = [vp, C.c_int]
     L.lo_odom_flush.restype = C.c_int
     L.lo_odom_flush.argtypes = [vp]
+    L.lo_loop_config_default.restype = None
+    L.lo_loop_config_default.argtypes = [C.POINTER(LoLoopConfig)]
+    L.lo_odom_enable_loop_closure.argtypes = [vp, C.POINTER(LoLoopConfig)]
+    L.lo_odom_last_loop.argtypes = [vp, C.POINTER(LoLoopEvent)]
+    L.lo_odom_loop_count.restype = C.c_size_t
+    L.lo_odom_loop_count.argtypes = [vp]
+    L.lo_odom_keyframe_poses.restype = C.c_size_t
+    L.lo_odom_keyframe_poses.argtypes = [vp, C.POINTER(C.c_int), fp, C.c_size_t]
+    L.lo_odom_build_map.argtypes = [vp, C.c_float, C.POINTER(C.c_size_t)]
+    L.lo_odom_map_points.restype = C.c_longlong
+    L.lo_odom_map_points.argtypes = [vp, fp, C.c_size_t]
+    L.lo_odom_save_map_ply.argtypes = [vp, C.c_char_p, C.c_float]
     L.lo_load_kitti_bin.restype = C.c_longlong
     L.lo_load_kitti_bin.argtypes = [C.c_char_p, fp, C.c_size_t]
     L.lo_load_ply.restype = C.c_longlong
@@ -331,6 +365,7 @@ def lib():
     L.lo_gmap_download.argtypes = [vp, fp, C.c_size_t]
     L.lo_gmap_device_points.argtypes = [vp, C.POINTER(vp), szp]
     L.lo_gmap_save_ply.argtypes = [vp, C.c_char_p]
+    L.lo_gmap_keyframe_points.argtypes = [vp, C.c_size_t, i64p, C.POINTER(vp), szp]
     L.lo_gmap_bench_build.argtypes = [vp, fp, C.c_size_t, C.c_float, C.c_int, fp]
     L.lo_gmap_stage_ms.argtypes = [vp, fp]
     L.lo_gmap_voxelgrid_host.restype = C.c_longlong

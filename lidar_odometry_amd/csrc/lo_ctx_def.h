@@ -43,7 +43,12 @@ struct PointGrid {
     float h = 1.0f;
 };
 
-// ctx_grid_from_device's scratch: the bounds readback, keys / values (and their sorted copies), cell counts, hipCUB temp
+// grid_from_device's scratch: the bounds readback, keys / values (and their sorted copies), cell counts, hipCUB temp.
+// d_bounds / h_bounds hold kGridWords 4-byte words: [0..5] the bounds, [6] the raw count, then
+constexpr int kGridOcc = 7;        // occupied cells (the min_per_cell rule)
+constexpr int kGridBad = 8;        // a non-finite world point (k_cloud_world)
+constexpr int kGridCount = 9;      // a host-known count handed to the device builder
+constexpr int kGridWords = 16;
 struct DevGridScratch {
     DevBuf<float> d_bounds;
     PinnedBuf<float> h_bounds;
@@ -132,6 +137,7 @@ struct lo_ctx {
     bool grid_dev = false;          // the grid was built on the device (no kd visit order; ties re-run, lo_icp_result)
     int kd_reruns = 0;              //   scans re-run with the order after such a tie (lo_kd_reruns)
     PointGrid lgrid;                // loop closure: the matched keyframe's local map (lo_icp_optimize_loop)
+    DevBuf<float> d_lworld;         //   a device-resident matched cloud in the world, before it is gridded (_loop_dev)
     uint64_t loop_reruns = 0;       //   solves rerun with the kd visit order (a deciding distance tie)
     DevBuf<int32_t> d_kd_nbr;
     DevBuf<int32_t> d_kd_unres;
@@ -197,6 +203,9 @@ extern uint64_t g_ticket;
 int grid_build(lo_ctx* c, PointGrid& G, const float* xyz, size_t m, bool with_order = true, int min_per_cell = 0);
 int all_pairs_upload(lo_ctx* c, PointGrid& G, const float* xyz, size_t m, const float* q = nullptr, size_t nq = 0);
 int grid_add_order(lo_ctx* c);
+int grid_add_order(lo_ctx* c, PointGrid& G, int min_per_cell);
+int grid_from_device(lo_ctx* c, PointGrid& G, const float* d_xyz, const int* d_count, size_t cap, int min_per_cell);
+int loop_map_from_device(lo_ctx* c, PointGrid& G, const float* d_xyz, size_t m, const float T[12], int min_per_cell);
 // lo_optimize.hip
 void launch_pko(lo_ctx* c, const KParams& P, int it);
 bool spec_ok(const KParams& P);

@@ -187,6 +187,7 @@ struct lo_gmap {
     hipStream_t stream = nullptr;
     size_t max_points = 0, max_keyframes = 0, max_chunks = 0;
     std::vector<int64_t> ids;
+    std::vector<size_t> kf_start, kf_n;  // each keyframe's first arena point and count
     std::vector<Chunk> chunks;           // host mirror of d_chunks
     size_t n_points = 0;
     // device buffers, all sized at create
@@ -233,6 +234,8 @@ static int gm_push(lo_gmap* m, int64_t id, size_t n) {
                                  hipMemcpyHostToDevice, m->stream));
     LO_HIP(m, hipStreamSynchronize(m->stream));               // the caller's buffer is free again
     m->ids.push_back(id);
+    m->kf_start.push_back(m->n_points);
+    m->kf_n.push_back(n);
     m->n_points += n;
     return LO_OK;
 }
@@ -362,6 +365,8 @@ size_t lo_gmap_points(const lo_gmap* m) { return m ? m->n_points : 0; }
 int lo_gmap_clear(lo_gmap* m) {
     if (!m) return LO_ERR_ARG;
     m->ids.clear();
+    m->kf_start.clear();
+    m->kf_n.clear();
     m->chunks.clear();
     m->n_points = 0;
     m->d_result = nullptr;
@@ -401,6 +406,15 @@ int lo_gmap_add_from_scan(lo_gmap* m, int64_t id) {
         LO_HIP(m, hipMemcpyAsync(m->d_arena + 3 * m->n_points, d_scan, static_cast<size_t>(n) * 3 * sizeof(float),
                                  hipMemcpyDeviceToDevice, m->stream));
     return gm_push(m, id, static_cast<size_t>(n));
+}
+
+int lo_gmap_keyframe_points(lo_gmap* m, size_t index, int64_t* id, const float** d_xyz, size_t* n) {
+    if (!m || !d_xyz || !n) return LO_ERR_ARG;
+    if (index >= m->ids.size()) { m->err = "keyframe index past the end"; return LO_ERR_ARG; }
+    if (id) *id = m->ids[index];
+    *d_xyz = m->d_arena + 3 * m->kf_start[index];
+    *n = m->kf_n[index];
+    return LO_OK;
 }
 
 int lo_gmap_build(lo_gmap* m, const float* poses, size_t n_poses, float voxel_size, size_t* out_n) {

@@ -1,5 +1,6 @@
 // lo_grid.hip — the KDTree variant's point grid: built on the host (grid_build, all_pairs_upload; lo_map_set_points)
-// or on the device from a device map's centroids (ctx_grid_from_device and its k_grid_* kernels).
+// or on the device (grid_from_device and its k_grid_* kernels: a device map's centroids through ctx_grid_from_device,
+// the loop-closure ICP's device-resident matched cloud through loop_map_from_device).
 #include <hipcub/hipcub.hpp>
 
 #include "lo_ctx_def.h"
@@ -164,8 +165,10 @@ struct GridGeom {
 };
 // grid_build's cell of a coordinate: floor(v / h) in fp32, as an int64 (the same operations)
 __device__ __forceinline__ long long grid_cell(float v, float h) { return static_cast<long long>(floorf(v / h)); }
+// occ (nullable): the number of occupied cells (grid_build's `occupied`, for the min_per_cell rule)
 __global__ void k_grid_keys(const float* __restrict__ xyz, const int* __restrict__ d_count, int cap, GridGeom g,
-                            uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t* __restrict__ counts) {
+                            uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t* __restrict__ counts,
+                            uint32_t* __restrict__ occ) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= min(*d_count, cap)) return;
     const long long x = grid_cell(xyz[3 * i], g.h) - g.org[0], y = grid_cell(xyz[3 * i + 1], g.h) - g.org[1],
@@ -173,7 +176,7 @@ __global__ void k_grid_keys(const float* __restrict__ xyz, const int* __restrict
     const uint32_t lin = static_cast<uint32_t>((static_cast<unsigned long long>(z) * g.dim[1] + y) * g.dim[0] + x);
     keys[i] = lin;
     vals[i] = static_cast<uint32_t>(i);
-    atomicAdd(&counts[lin], 1u);
+    if (atomicAdd(&counts[lin], 1u) == 0u && occ) atomicAdd(occ, 1u);
 }
 __global__ void k_grid_scatter(const float* __restrict__ xyz, const int* __restrict__ d_count, int cap,
                                const uint32_t* __restrict__ svals, float4* __restrict__ pts) {
@@ -183,17 +186,23 @@ __global__ void k_grid_scatter(const float* __restrict__ xyz, const int* __restr
     pts[p] = make_float4(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], __int_as_float(static_cast<int>(i)));
 }
 
-int ctx_grid_from_device(lo_ctx* c, const float* d_xyz, const int* d_count, size_t cap) {
-    if (!c || !d_xyz || !d_count) return LO_ERR_ARG;
-    if (!c->kd) { c->err = "ctx_grid_from_device: a KDTree-mode context"; return LO_ERR_STATE; }
-    LO_HIP(c, hipSetDevice(c->device));
-    PointGrid& G = c->grid;
+// The scratch words behind the six bounds and the count (DevGridScratch::d_bounds / h_bounds, kGridWords floats).
+int grid_scratch(lo_ctx* c) {
+    LO_HIP(c, c->gscr.d_bounds.reserve(kGridWords));
+    LO_HIP(c, c->gscr.h_bounds.reserve(kGridWords));
+    return LO_OK;
+}
+
+// grid_build's grid of a device point array, into G.  min_per_cell as grid_build: the cell edge doubles (up to 3
+// times) while the occupied cells hold fewer points on average -- the occupied count is one more 4-byte readback per
+// doubling step.
+int grid_from_device(lo_ctx* c, PointGrid& G, const float* d_xyz, const int* d_count, size_t cap, int min_per_cell) {
     DevGridScratch& S = c->gscr;
-    LO_HIP(c, S.d_bounds.reserve(8));
-    LO_HIP(c, S.h_bounds.reserve(8));
+    int rc = grid_scratch(c);
+    if (rc != LO_OK) return rc;
     const int capi = static_cast<int>(std::min(cap, static_cast<size_t>(INT32_MAX)));
     hipLaunchKernelGGL(k_grid_bounds, dim3(1), dim3(1024), 0, c->stream, d_xyz, d_count, capi, S.d_bounds);
-    LO_HIP(c, hipMemcpyAsync(S.h_bounds, S.d_bounds, 8 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    LO_HIP(c, hipMemcpyAsync(S.h_bounds, S.d_bounds, 7 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     LO_HIP(c, hipStreamSynchronize(c->stream));
     int mi = 0;
     std::memcpy(&mi, &S.h_bounds[6], sizeof(int));
@@ -204,30 +213,48 @@ int ctx_grid_from_device(lo_ctx* c, const float* d_xyz, const int* d_count, size
     float h = 2.0f * c->cfg.voxel_size;
     int org[3] = {0, 0, 0}, dim[3] = {1, 1, 1};
     auto cell = [&](float v) { return static_cast<int64_t>(std::floor(v / h)); };
-    for (;;) {
-        int64_t lo[3], hi[3];
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = m ? cell(S.h_bounds[a]) : 0;
-            hi[a] = m ? cell(S.h_bounds[3 + a]) : 0;
-        }
-        size_t ncell = 1;
-        bool ok = true;
-        for (int a = 0; a < 3; ++a) {
-            const int64_t d = hi[a] - lo[a] + 1;
-            if (d > static_cast<int64_t>(kKdMaxCells) || lo[a] < INT32_MIN / 2 || hi[a] > INT32_MAX / 2) { ok = false; break; }
-            ncell *= static_cast<size_t>(d);
-            if (ncell > kKdMaxCells) { ok = false; break; }
-        }
-        if (ok) { for (int a = 0; a < 3; ++a) { org[a] = static_cast<int>(lo[a]); dim[a] = static_cast<int>(hi[a] - lo[a] + 1); } break; }
-        h *= 2.0f;
-    }
-    const size_t ncell = static_cast<size_t>(dim[0]) * dim[1] * dim[2];
     const size_t mm = std::max<size_t>(m, 1);
     LO_HIP(c, G.d_pts.reserve(mm));
-    LO_HIP(c, G.d_start.reserve(ncell + 1));
     LO_HIP(c, S.d_keys.reserve(4 * mm));                 // keys, vals, sorted keys, sorted vals
-    LO_HIP(c, S.d_counts.reserve(ncell + 1));
     uint32_t *keys = S.d_keys, *vals = keys + mm, *skeys = vals + mm, *svals = skeys + mm;
+    uint32_t* d_occ = reinterpret_cast<uint32_t*>(S.d_bounds.get()) + kGridOcc;
+    const dim3 grid((mm + 255) / 256), blk(256);
+    size_t ncell = 1;
+    for (int grow = 0;; ++grow) {
+        for (;;) {
+            int64_t lo[3], hi[3];
+            for (int a = 0; a < 3; ++a) {
+                lo[a] = m ? cell(S.h_bounds[a]) : 0;
+                hi[a] = m ? cell(S.h_bounds[3 + a]) : 0;
+            }
+            ncell = 1;
+            bool ok = true;
+            for (int a = 0; a < 3; ++a) {
+                const int64_t d = hi[a] - lo[a] + 1;
+                if (d > static_cast<int64_t>(kKdMaxCells) || lo[a] < INT32_MIN / 2 || hi[a] > INT32_MAX / 2) { ok = false; break; }
+                ncell *= static_cast<size_t>(d);
+                if (ncell > kKdMaxCells) { ok = false; break; }
+            }
+            if (ok) { for (int a = 0; a < 3; ++a) { org[a] = static_cast<int>(lo[a]); dim[a] = static_cast<int>(hi[a] - lo[a] + 1); } break; }
+            h *= 2.0f;
+        }
+        LO_HIP(c, G.d_start.reserve(ncell + 1));
+        LO_HIP(c, S.d_counts.reserve(ncell + 1));
+        LO_HIP(c, hipMemsetAsync(S.d_counts, 0, (ncell + 1) * sizeof(uint32_t), c->stream));
+        const bool sparse_rule = min_per_cell > 0 && grow < 3 && m >= 64;
+        if (sparse_rule) LO_HIP(c, hipMemsetAsync(d_occ, 0, sizeof(uint32_t), c->stream));
+        const GridGeom g{h, {org[0], org[1], org[2]}, {dim[0], dim[1], dim[2]}};
+        if (m > 0)
+            hipLaunchKernelGGL(k_grid_keys, grid, blk, 0, c->stream, d_xyz, d_count, capi, g, keys, vals, S.d_counts.get(),
+                               sparse_rule ? d_occ : nullptr);
+        if (!sparse_rule) break;
+        LO_HIP(c, hipMemcpyAsync(S.h_bounds + kGridOcc, d_occ, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        LO_HIP(c, hipStreamSynchronize(c->stream));
+        uint32_t occupied = 0;
+        std::memcpy(&occupied, &S.h_bounds[kGridOcc], sizeof(uint32_t));
+        if (static_cast<size_t>(occupied) * static_cast<size_t>(min_per_cell) > m) { h *= 2.0f; continue; }
+        break;
+    }
     int bits = 1;
     while (bits < 32 && (size_t(1) << bits) < ncell) ++bits;
     size_t tmp_sort = 0, tmp_scan = 0;
@@ -236,15 +263,11 @@ int ctx_grid_from_device(lo_ctx* c, const float* d_xyz, const int* d_count, size
     LO_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_scan, S.d_counts.get(), G.d_start.get(), static_cast<int>(ncell + 1),
                                                c->stream));
     LO_HIP(c, S.d_tmp.reserve(std::max(tmp_sort, tmp_scan)));
-    LO_HIP(c, hipMemsetAsync(S.d_counts, 0, (ncell + 1) * sizeof(uint32_t), c->stream));
-    GridGeom g{h, {org[0], org[1], org[2]}, {dim[0], dim[1], dim[2]}};
     if (m > 0) {
-        const dim3 grid((m + 255) / 256), blk(256);
-        hipLaunchKernelGGL(k_grid_keys, grid, blk, 0, c->stream, d_xyz, d_count, capi, g, keys, vals, S.d_counts);
         size_t t = S.d_tmp.capacity();
         LO_HIP(c, hipcub::DeviceRadixSort::SortPairs(S.d_tmp, t, keys, skeys, vals, svals, static_cast<int>(m), 0, bits,
                                                      c->stream));
-        hipLaunchKernelGGL(k_grid_scatter, grid, blk, 0, c->stream, d_xyz, d_count, capi, svals, G.d_pts);
+        hipLaunchKernelGGL(k_grid_scatter, grid, blk, 0, c->stream, d_xyz, d_count, capi, svals, G.d_pts.get());
     }
     size_t t2 = S.d_tmp.capacity();                           // start[cell] = points in the cells before it; start[ncell] = m
     LO_HIP(c, hipcub::DeviceScan::ExclusiveSum(S.d_tmp, t2, S.d_counts.get(), G.d_start.get(), static_cast<int>(ncell + 1), c->stream));
@@ -254,8 +277,75 @@ int ctx_grid_from_device(lo_ctx* c, const float* d_xyz, const int* d_count, size
     G.all = false;
     G.h = h;
     for (int a = 0; a < 3; ++a) { G.org[a] = org[a]; G.dim[a] = dim[a]; }
-    c->grid_dev = true;
     return LO_OK;
+}
+
+// A device cloud (sensor frame, AoS float3) in the world: transform_pt, util::transform_point_cloud's fp32 order, as
+// lo::transform_points on the host.  ALL: float4 (x, y, z, index) in index order (all_pairs_upload's layout); else
+// float3.  words: the grid scratch -- [kGridCount] receives n (the device count grid_from_device reads), [kGridBad]
+// is raised by a non-finite world point (grid_build's LO_ERR_ARG).
+template <bool ALL>
+__global__ __launch_bounds__(kBlock) void k_cloud_world(const float* __restrict__ in, int n, Pose12 T,
+                                                        float* __restrict__ out3, float4* __restrict__ out4,
+                                                        uint32_t* __restrict__ words) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i == 0) words[kGridCount] = static_cast<uint32_t>(n);
+    if (i >= n) return;
+    float wx, wy, wz;
+    transform_pt(T.v, in[3 * static_cast<size_t>(i)], in[3 * static_cast<size_t>(i) + 1], in[3 * static_cast<size_t>(i) + 2],
+                 wx, wy, wz);
+    if (!(isfinite(wx) && isfinite(wy) && isfinite(wz))) atomicOr(&words[kGridBad], 1u);
+    if (ALL) {
+        out4[i] = make_float4(wx, wy, wz, __int_as_float(i));
+    } else {
+        out3[3 * static_cast<size_t>(i)] = wx;
+        out3[3 * static_cast<size_t>(i) + 1] = wy;
+        out3[3 * static_cast<size_t>(i) + 2] = wz;
+    }
+}
+
+// The loop-closure ICP's local map from a device cloud: d_xyz (m points, sensor frame) at pose T, into G -- the
+// all-pairs layout up to kKnnAllMax points, else grid_build's grid (no visit order either way), as all_pairs_upload /
+// grid_build give for the same cloud transformed on the host.
+int loop_map_from_device(lo_ctx* c, PointGrid& G, const float* d_xyz, size_t m, const float T[12], int min_per_cell) {
+    if (m > 0 && !d_xyz) { c->err = "null points"; return LO_ERR_ARG; }
+    if (m > static_cast<size_t>(INT32_MAX / 2)) { c->err = "too many map points"; return LO_ERR_CAPACITY; }
+    int rc = grid_scratch(c);
+    if (rc != LO_OK) return rc;
+    LO_HIP(c, hipStreamSynchronize(c->stream));          // nothing in flight reads the buffers grown below
+    const bool all = m <= static_cast<size_t>(kKnnAllMax);
+    const size_t mm = std::max<size_t>(m, 1);
+    if (all) LO_HIP(c, G.d_pts.reserve(mm));
+    else LO_HIP(c, c->d_lworld.reserve(3 * mm));
+    uint32_t* words = reinterpret_cast<uint32_t*>(c->gscr.d_bounds.get());
+    LO_HIP(c, hipMemsetAsync(words + kGridBad, 0, sizeof(uint32_t), c->stream));
+    Pose12 P;
+    std::memcpy(P.v, T, sizeof(P.v));
+    const dim3 grid(static_cast<unsigned>((mm + kBlock - 1) / kBlock)), blk(kBlock);
+    if (all) hipLaunchKernelGGL(k_cloud_world<true>, grid, blk, 0, c->stream, d_xyz, static_cast<int>(m), P, nullptr, G.d_pts.get(), words);
+    else hipLaunchKernelGGL(k_cloud_world<false>, grid, blk, 0, c->stream, d_xyz, static_cast<int>(m), P, c->d_lworld.get(), nullptr, words);
+    LO_HIP(c, hipGetLastError());
+    LO_HIP(c, hipMemcpyAsync(c->gscr.h_bounds + kGridBad, words + kGridBad, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    LO_HIP(c, hipStreamSynchronize(c->stream));
+    uint32_t bad = 0;
+    std::memcpy(&bad, &c->gscr.h_bounds[kGridBad], sizeof(uint32_t));
+    if (bad) { c->err = "non-finite map point"; return LO_ERR_ARG; }
+    if (all) {
+        G.m = static_cast<int>(m);
+        G.has_order = false;
+        G.all = true;
+        return LO_OK;
+    }
+    return grid_from_device(c, G, c->d_lworld, reinterpret_cast<const int*>(words + kGridCount), m, min_per_cell);
+}
+
+int ctx_grid_from_device(lo_ctx* c, const float* d_xyz, const int* d_count, size_t cap) {
+    if (!c || !d_xyz || !d_count) return LO_ERR_ARG;
+    if (!c->kd) { c->err = "ctx_grid_from_device: a KDTree-mode context"; return LO_ERR_STATE; }
+    LO_HIP(c, hipSetDevice(c->device));
+    const int rc = grid_from_device(c, c->grid, d_xyz, d_count, cap, 0);
+    if (rc == LO_OK) c->grid_dev = true;
+    return rc;
 }
 
 }  // namespace lo
@@ -272,10 +362,10 @@ int lo_map_set_points(lo_ctx* c, const float* xyz, size_t m) {
 }  // extern "C"
 
 namespace lo {
-// The kd visit order for a device-built grid (ctx_grid_from_device): its points back in index order (each grid
-// point carries its index), then the host build with the order -- the same grid plus the order.
-int grid_add_order(lo_ctx* c) {
-    PointGrid& G = c->grid;
+// The kd visit order for a grid whose points are on the device only (grid_from_device, all_pairs_device): its points
+// back in index order (each grid point carries its index), then the host build with the order -- the same grid plus
+// the order.
+int grid_add_order(lo_ctx* c, PointGrid& G, int min_per_cell) {
     const size_t m = static_cast<size_t>(G.m);
     std::vector<float4> p(std::max<size_t>(m, 1));
     LO_HIP(c, hipStreamSynchronize(c->stream));
@@ -287,7 +377,10 @@ int grid_add_order(lo_ctx* c) {
         if (i < 0 || static_cast<size_t>(i) >= m) { c->err = "device grid: bad point index"; return LO_ERR_STATE; }
         xyz[3 * i] = p[k].x; xyz[3 * i + 1] = p[k].y; xyz[3 * i + 2] = p[k].z;
     }
-    const int rc = grid_build(c, G, xyz.data(), m, true);
+    return grid_build(c, G, xyz.data(), m, true, min_per_cell);
+}
+int grid_add_order(lo_ctx* c) {
+    const int rc = grid_add_order(c, c->grid, 0);
     if (rc == LO_OK) c->grid_dev = true;                 // still the device map's grid (the next keyframe rebuilds it)
     return rc;
 }
@@ -296,6 +389,7 @@ int grid_add_order(lo_ctx* c) {
 extern "C" {
 
 int lo_kd_reruns(const lo_ctx* c) { return c ? c->kd_reruns : -1; }
+long long lo_loop_reruns(const lo_ctx* c) { return c ? static_cast<long long>(c->loop_reruns) : -1; }
 
 size_t lo_map_point_count(const lo_ctx* c) { return c ? static_cast<size_t>(c->grid.m) : 0; }
 

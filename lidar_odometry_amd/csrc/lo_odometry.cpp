@@ -1,4 +1,4 @@
-// lo_odometry.cpp — Estimator::process_frame without loop closure / PGO (see include/lo_odometry.h), host C++
+// lo_odometry.cpp — Estimator::process_frame, with opt-in loop closure / PGO (see include/lo_odometry.h), host C++
 // driving the device path: each frame is one lo_icp_optimize_raw call (device voxel filter + GN loop); the
 // pose bookkeeping uses the reference's SE3f algebra (lo_math.h); keyframes update the voxel map: in surfel mode the
 // device-resident map (lo_devmap: the filtered scan never leaves the device, the context's table is patched in
@@ -12,8 +12,11 @@
 #include <string>
 #include <vector>
 
+#include "../../include/lo_gmap.h"
 #include "../../include/lo_map.h"
 #include "../../include/lo_odometry.h"
+#include "../../include/lo_pgo.h"
+#include "lo_ctx_internal.h"
 #include "lo_math.h"
 
 using lo::SE3f;
@@ -28,7 +31,127 @@ struct lo_odometry {
     SE3f initial, prev, velocity, last_kf;
     size_t keyframes = 0;
     std::vector<float> feat, world;
+    // loop closure (lo_odom_enable_loop_closure); all null / empty otherwise
+    bool loop_on = false;
+    lo_loop_config lcfg{};
+    lo_iris* iris = nullptr;
+    lo_gmap* gmap = nullptr;
+    lo_pgo* pgo = nullptr;
+    std::vector<SE3f> kf_poses;           // the keyframes' current (corrected) poses; keyframe id = index
+    int last_loop_kf = -1;                // m_last_successful_loop_keyframe_id (Estimator.cpp:38)
+    size_t loops = 0;
+    lo_loop_event ev{};
+    long long last_nf = 0;                // the current frame's filtered count
 };
+
+static double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// ApplyTransformAndRehash(correction) on whichever map the loop keeps (apply_pending_pgo_result_if_available, step 3)
+static int loop_move_map(lo_odometry* o, const SE3f& corr) {
+    float T[12];
+    lo::se3_to12(corr, T);
+    if (o->dmap) {
+        int rc = lo_devmap_apply_transform(o->dmap, T);
+        if (rc == LO_OK && !o->cfg.icp.use_surfel_correspondence) rc = lo_devmap_sync_points(o->dmap);
+        if (rc == LO_OK) rc = lo_devmap_status_async(o->dmap);
+        if (rc != LO_OK) o->err = lo_devmap_last_error(o->dmap);
+        return rc;
+    }
+    int rc = lo_voxelmap_apply_transform(o->map, T);
+    if (rc == LO_OK) rc = lo_map_sync_voxelmap(o->icp, o->map, nullptr);
+    if (rc != LO_OK) o->err = "loop closure: map correction failed";
+    return rc;
+}
+
+// The loop bookkeeping of one new keyframe (id = its index) at `pose`, after its map update: create_keyframe's PGO /
+// detector part (:399-421, :496-517), then -- synchronously -- run_pgo_for_loop and the application of its result.
+static int loop_on_keyframe(lo_odometry* o, const SE3f& pose) {
+    const int id = static_cast<int>(o->kf_poses.size());
+    lo_loop_event& ev = o->ev;
+    ev = lo_loop_event{};
+    ev.keyframe_id = id;
+    ev.candidate_id = -1;
+    ev.icp_status = LO_INSUFFICIENT;
+    float T[12];
+    lo::se3_to12(pose, T);
+    int rc = lo_gmap_add_from_scan(o->gmap, id);
+    if (rc != LO_OK) { o->err = std::string("loop closure keyframe store: ") + lo_gmap_last_error(o->gmap); return rc; }
+    if (id == 0) {
+        lo_pgo_add_first_keyframe(o->pgo, id, T);
+    } else {
+        float rel[12];
+        lo::se3_to12(lo::se3_mul(lo::se3_inv(o->kf_poses.back()), pose), rel);
+        lo_pgo_add_keyframe_with_odom(o->pgo, id - 1, id, T, rel, o->lcfg.odom_trans_noise, o->lcfg.odom_rot_noise);
+    }
+    o->kf_poses.push_back(pose);
+    const size_t n_curr = static_cast<size_t>(std::max<long long>(o->last_nf, 0));
+    const float* d_curr = nullptr;
+    const int* d_n = nullptr;
+    if (lo::ctx_filtered_device(o->icp, &d_curr, &d_n) != LO_OK) { o->err = lo_last_error(o->icp); return LO_ERR_STATE; }
+    lo_iris_candidate cand{};
+    bool have = false;
+    if (id - o->last_loop_kf >= o->lcfg.cooldown_keyframes) {
+        const auto t0 = std::chrono::steady_clock::now();
+        ev.queried = 1;
+        rc = lo_iris_detect(o->iris, &o->lcfg.iris, id, pose.t, d_curr, n_curr, 1, &cand);
+        ev.detect_ms = ms_since(t0);
+        if (rc < 0) { o->err = std::string("loop detector: ") + lo_iris_last_error(o->iris); return rc; }
+        have = rc == LO_OK;
+    }
+    rc = lo_iris_add_from_scan(o->iris, id, pose.t);        // (LO_INSUFFICIENT: an empty cloud is not added)
+    if (rc < 0) { o->err = std::string("loop detector: ") + lo_iris_last_error(o->iris); return rc; }
+    if (!have) return LO_OK;
+    ev.candidate_id = static_cast<int>(cand.match_keyframe_id);
+    ev.candidate_distance = cand.distance;
+    ev.candidate_bias = cand.bias;
+    const int mid = ev.candidate_id;
+    if (mid < 0 || mid >= id) { o->err = "loop detector: candidate id out of range"; return LO_ERR_STATE; }
+    const float* d_m = nullptr;
+    size_t n_m = 0;
+    rc = lo_gmap_keyframe_points(o->gmap, static_cast<size_t>(mid), nullptr, &d_m, &n_m);
+    if (rc != LO_OK) { o->err = lo_gmap_last_error(o->gmap); return rc; }
+    if (n_m == 0 || n_curr == 0) return LO_OK;               // "Empty feature clouds for loop" (:989-995)
+    float Tm[12], Trel[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    lo::se3_to12(o->kf_poses[mid], Tm);
+    lo_stats st{};
+    float inl = 0.0f;
+    const auto t1 = std::chrono::steady_clock::now();
+    rc = lo_icp_optimize_loop_dev(o->icp, d_curr, n_curr, T, d_m, n_m, Tm, Trel, &inl, nullptr, &st);
+    ev.icp_ms = ms_since(t1);
+    if (rc < 0) { o->err = lo_last_error(o->icp); return rc; }
+    ev.icp_status = rc;
+    ev.icp_iterations = st.iterations;
+    ev.inlier_ratio = st.converged ? inl : 0.0f;
+    if (rc != LO_OK || inl < o->lcfg.min_inlier_ratio) return LO_OK;          // :1008-1020
+    const SE3f corrected = lo::se3_mul(pose, lo::se3_from12(Trel));            // :1027
+    float con[12];
+    lo::se3_to12(lo::se3_mul(lo::se3_inv(o->kf_poses[mid]), corrected), con);  // :1039
+    const auto t2 = std::chrono::steady_clock::now();
+    const int ok = lo_pgo_add_loop_and_optimize(o->pgo, mid, id, con, o->lcfg.loop_trans_noise, o->lcfg.loop_rot_noise,
+                                                &ev.pgo_converged, &ev.pgo_iterations, nullptr);
+    ev.pgo_ms = ms_since(t2);
+    if (ok != 1) return LO_OK;                                                 // "PGO failed!" (:1080-1083)
+    // apply_pending_pgo_result_if_available, here and now: poses, map, previous-frame pose, cooldown
+    const SE3f before = o->kf_poses.back();
+    for (int k = 0; k <= id; ++k) {
+        float P[12];
+        if (lo_pgo_get_optimized_pose(o->pgo, k, P) == 1) o->kf_poses[k] = lo::se3_from12(P);
+    }
+    const SE3f corr = lo::se3_mul(o->kf_poses.back(), lo::se3_inv(before));    // :1121
+    ev.correction_translation = std::sqrt(lo::dot3e(corr.t[0], corr.t[1], corr.t[2], corr.t[0], corr.t[1], corr.t[2]));
+    ev.correction_angle = lo::so3_log_norm(corr.R);
+    const auto t3 = std::chrono::steady_clock::now();
+    rc = loop_move_map(o, corr);
+    ev.map_ms = ms_since(t3);
+    if (rc != LO_OK) return rc;
+    o->prev = o->kf_poses.back();                            // m_previous_frame is this keyframe; m_velocity is kept;
+    o->last_loop_kf = id;                                    // m_last_keyframe_pose (o->last_kf) is NOT moved (:494)
+    ++o->loops;
+    ev.accepted = 1;
+    return LO_OK;
+}
 
 static int create_keyframe(lo_odometry* o, const SE3f& pose, lo_odom_frame* info) {
     // create_keyframe (:370-530): world feature cloud -> UpdateVoxelMap(cloud, position, 1.2 max_range) -> device
@@ -52,7 +175,7 @@ static int create_keyframe(lo_odometry* o, const SE3f& pose, lo_odom_frame* info
             info->keyframe = 1;
             info->map_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         }
-        return LO_OK;
+        return o->loop_on ? loop_on_keyframe(o, pose) : LO_OK;
     }
     const long long n = lo_filtered_points(o->icp, nullptr, 0);
     if (n < 0) { o->err = lo_last_error(o->icp); return static_cast<int>(n); }
@@ -70,7 +193,7 @@ static int create_keyframe(lo_odometry* o, const SE3f& pose, lo_odom_frame* info
         info->keyframe = 1;
         info->map_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
-    return LO_OK;
+    return o->loop_on ? loop_on_keyframe(o, pose) : LO_OK;
 }
 
 extern "C" {
@@ -112,6 +235,9 @@ lo_odometry* lo_odom_create(const lo_odom_config* cfg, int device, int* err) {
 
 void lo_odom_destroy(lo_odometry* o) {
     if (!o) return;
+    lo_iris_destroy(o->iris);                            // the three loop-closure handles go before their context
+    lo_gmap_destroy(o->gmap);
+    lo_pgo_destroy(o->pgo);
     lo_devmap_destroy(o->dmap);
     lo_voxelmap_destroy(o->map);
     lo_destroy(o->icp);
@@ -144,6 +270,7 @@ int lo_odom_process(lo_odometry* o, const float* raw, size_t n, float T_out[12],
         const long long nf = lo_voxel_filter_gpu(o->icp, raw, n, voxel, stride, nullptr, 0);
         if (nf < 0) { o->err = lo_last_error(o->icp); return static_cast<int>(nf); }
         fi->n_filtered = static_cast<int>(nf);
+        o->last_nf = nf;
         o->prev = o->initial;
         o->velocity = SE3f();
         if (nf > 0) {
@@ -183,6 +310,7 @@ int lo_odom_process(lo_odometry* o, const float* raw, size_t n, float T_out[12],
     fi->device_ms = st.gpu_ms;
     const long long nf = lo_filtered_points(o->icp, nullptr, 0);
     fi->n_filtered = static_cast<int>(nf > 0 ? nf : 0);
+    o->last_nf = nf;
     SE3f pose = guess;
     if (rc == LO_OK) {
         const SE3f r = lo::se3_from12(p12);
@@ -202,7 +330,7 @@ int lo_odom_process(lo_odometry* o, const float* raw, size_t n, float T_out[12],
     lo::so3_project_svd(Rrel, Rrel_p);                                            // SO3::operator*
     const double ang = lo::so3_log_norm(Rrel_p);
     if (static_cast<double>(dist) > o->cfg.keyframe_distance || ang > o->cfg.keyframe_rotation) {
-        const int krc = create_keyframe(o, pose, fi);
+        const int krc = create_keyframe(o, pose, fi);       // (a closed loop moves o->prev, not this frame's pose)
         if (krc != LO_OK) return krc;
     }
     std::memcpy(T_out, p12, sizeof(p12));
@@ -214,6 +342,94 @@ int lo_odom_flush(lo_odometry* o) {
     if (!o->dmap) return LO_OK;                          // the host map reports inside lo_voxelmap_update
     const int rc = lo_devmap_status(o->dmap);            // synchronous: the last update's error bits
     if (rc != LO_OK) o->err = lo_devmap_last_error(o->dmap);
+    return rc;
+}
+
+void lo_loop_config_default(lo_loop_config* c) {
+    if (!c) return;
+    std::memset(c, 0, sizeof(*c));
+    lo_iris_config_default(&c->iris);
+    c->cooldown_keyframes = 50;
+    c->min_inlier_ratio = 0.3f;
+    c->odom_trans_noise = 0.5;
+    c->odom_rot_noise = 0.5;
+    c->loop_trans_noise = 1.0;
+    c->loop_rot_noise = 1.0;
+    c->max_keyframes = 4096;
+    c->max_points = size_t(1) << 22;
+}
+
+int lo_odom_enable_loop_closure(lo_odometry* o, const lo_loop_config* cfg) {
+    if (!o || !cfg) return LO_ERR_ARG;
+    if (cfg->iris.min_keyframe_gap < 1 || cfg->max_keyframes < 1 || cfg->max_points < 1) {
+        o->err = "loop closure: min_keyframe_gap, max_keyframes and max_points must be >= 1";
+        return LO_ERR_ARG;
+    }
+    if (o->initialized || o->loop_on) { o->err = "loop closure is enabled once, before the first frame"; return LO_ERR_STATE; }
+    int e = LO_OK;
+    lo_iris* iris = lo_iris_create(o->icp, cfg->max_keyframes, &e);
+    lo_gmap* gmap = iris ? lo_gmap_create(o->icp, cfg->max_points, cfg->max_keyframes, &e) : nullptr;
+    lo_pgo* pgo = gmap ? lo_pgo_create() : nullptr;
+    if (!pgo) {
+        lo_gmap_destroy(gmap);
+        lo_iris_destroy(iris);
+        o->err = "loop closure: allocation failed";
+        return e != LO_OK ? e : LO_ERR_HIP;
+    }
+    o->iris = iris;
+    o->gmap = gmap;
+    o->pgo = pgo;
+    o->lcfg = *cfg;
+    o->ev = lo_loop_event{};
+    o->ev.keyframe_id = -1;
+    o->ev.candidate_id = -1;
+    o->loop_on = true;
+    return LO_OK;
+}
+
+int lo_odom_last_loop(const lo_odometry* o, lo_loop_event* out) {
+    if (!o || !out) return LO_ERR_ARG;
+    if (!o->loop_on) return LO_ERR_STATE;
+    *out = o->ev;
+    return LO_OK;
+}
+
+size_t lo_odom_loop_count(const lo_odometry* o) { return o ? o->loops : 0; }
+
+size_t lo_odom_keyframe_poses(const lo_odometry* o, int* ids, float* poses, size_t cap) {
+    if (!o) return 0;
+    const size_t n = o->kf_poses.size();
+    for (size_t k = 0; k < n && k < cap; ++k) {
+        if (ids) ids[k] = static_cast<int>(k);
+        if (poses) lo::se3_to12(o->kf_poses[k], poses + 12 * k);
+    }
+    return n;
+}
+
+int lo_odom_build_map(lo_odometry* o, float voxel_size, size_t* out_n) {
+    if (!o) return LO_ERR_ARG;
+    if (!o->loop_on) { o->err = "loop closure is not enabled"; return LO_ERR_STATE; }
+    std::vector<float> P(12 * std::max<size_t>(o->kf_poses.size(), 1));
+    for (size_t k = 0; k < o->kf_poses.size(); ++k) lo::se3_to12(o->kf_poses[k], P.data() + 12 * k);
+    const int rc = lo_gmap_build(o->gmap, P.data(), o->kf_poses.size(), voxel_size, out_n);
+    if (rc < 0) o->err = lo_gmap_last_error(o->gmap);
+    return rc;
+}
+
+long long lo_odom_map_points(lo_odometry* o, float* out, size_t cap) {
+    if (!o) return LO_ERR_ARG;
+    if (!o->loop_on) { o->err = "loop closure is not enabled"; return LO_ERR_STATE; }
+    const long long k = lo_gmap_download(o->gmap, out, cap);
+    if (k < 0) o->err = lo_gmap_last_error(o->gmap);
+    return k;
+}
+
+int lo_odom_save_map_ply(lo_odometry* o, const char* path, float voxel_size) {
+    if (!o || !path) return LO_ERR_ARG;
+    int rc = lo_odom_build_map(o, voxel_size, nullptr);
+    if (rc != LO_OK) return rc;                          // (LO_INSUFFICIENT: nothing stored, nothing written)
+    rc = lo_gmap_save_ply(o->gmap, path);
+    if (rc < 0) o->err = lo_gmap_last_error(o->gmap);
     return rc;
 }
 

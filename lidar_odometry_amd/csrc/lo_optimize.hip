@@ -468,32 +468,25 @@ static constexpr int kLoopMaxIters = 100;                // :74
 static constexpr int kLoopChunk = 4;
 static constexpr int kLoopMinPerCell = 4;                // the matched cloud's grid: >= 4 points per occupied cell
 
-int lo_icp_optimize_loop(lo_ctx* c, const float* curr, size_t n_curr, const float T_curr[12], const float* matched,
-                         size_t n_matched, const float T_matched[12], float T_rel_out[12], float* inlier_ratio,
-                         lo_iter_log* logs, lo_stats* st) {
-    if (!c || !T_curr || !T_matched || !T_rel_out || !inlier_ratio || (n_curr > 0 && !curr) || (n_matched > 0 && !matched))
-        return LO_ERR_ARG;
-    if (n_curr > static_cast<size_t>(c->cfg.max_points)) { c->err = "n_curr exceeds max_points"; return LO_ERR_CAPACITY; }
-    LO_HIP(c, hipSetDevice(c->device));
-    int rc = kd_alloc(c);
-    if (rc != LO_OK) return rc;
-    // local map of the matched keyframe: its feature cloud in the world (transform_point_cloud, :60-64)
-    const lo::SE3f Tm = lo::se3_from12(T_matched);
-    std::vector<float> lmap(3 * std::max<size_t>(n_matched, 1));
-    if (n_matched > 0) lo::transform_points(Tm, matched, n_matched, lmap.data());
-    // the matched cloud's grid first without the kd visit order (building it is ~0.3 ms of host work per call and
-    // it only ranks exact distance ties that decide a query's five neighbours or their order, which keyframe
-    // centroids rarely produce); a solve that met one is rerun with the order below
+// The solve shared by both entry points, after the matched cloud's local map sits in c->lgrid (built without the kd
+// visit order).  curr: the current cloud, a host pointer or (curr_dev) a device pointer -- c->d_pts itself is used in
+// place; lmap: the matched cloud in the world on the host, or null when it exists on the device only (a rerun with
+// the visit order then brings the gridded points down, grid_add_order).
+static int loop_solve(lo_ctx* c, const float* curr, bool curr_dev, size_t n_curr, const float T_curr[12], const float* lmap,
+                      size_t n_matched, const float T_matched[12], float T_rel_out[12], float* inlier_ratio,
+                      lo_iter_log* logs, lo_stats* st) {
+    int rc = LO_OK;
     bool with_order = false;
-    const bool all = n_matched <= static_cast<size_t>(kKnnAllMax);     // (the clouds' pinned upload, curr included)
-    rc = all ? all_pairs_upload(c, c->lgrid, lmap.data(), n_matched, curr, n_curr)
-             : grid_build(c, c->lgrid, lmap.data(), n_matched, with_order, kLoopMinPerCell);
-    if (rc != LO_OK) return rc;
+    // all_pairs_upload has put a host cloud into c->d_pts already; every other case copies it below
+    bool curr_staged = !curr_dev && c->lgrid.all;
 retry:
     if (st) { std::memset(st, 0, sizeof(*st)); st->status = LO_INSUFFICIENT; }
     if (n_curr == 0 || n_matched == 0) return LO_INSUFFICIENT;       // empty clouds: 0 correspondences (:477-483)
     if ((rc = ensure_acc_part(c)) != LO_OK) return rc;
-    if (!c->lgrid.all) LO_HIP(c, hipMemcpyAsync(c->d_pts, curr, n_curr * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (!curr_staged && curr != c->d_pts.get())
+        LO_HIP(c, hipMemcpyAsync(c->d_pts, curr, n_curr * 3 * sizeof(float),
+                                 curr_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    curr_staged = false;                                 // (a rerun copies it again, as it always has)
     KParams P = make_params(c, c->d_pts, static_cast<int>(n_curr));
     set_kd_params(c, P, c->lgrid);
     P.loop = 1;
@@ -554,7 +547,8 @@ retry:
     if (c->h_st->kd_tie && !with_order) {               // a deciding tie was ranked by index: redo with the order
         with_order = true;
         ++c->loop_reruns;
-        rc = grid_build(c, c->lgrid, lmap.data(), n_matched, true, kLoopMinPerCell);
+        rc = lmap ? grid_build(c, c->lgrid, lmap, n_matched, true, kLoopMinPerCell)
+                  : grid_add_order(c, c->lgrid, kLoopMinPerCell);
         if (rc != LO_OK) return rc;
         goto retry;
     }
@@ -584,6 +578,46 @@ retry:
     }
     c->pending = false;
     return status;
+}
+
+int lo_icp_optimize_loop(lo_ctx* c, const float* curr, size_t n_curr, const float T_curr[12], const float* matched,
+                         size_t n_matched, const float T_matched[12], float T_rel_out[12], float* inlier_ratio,
+                         lo_iter_log* logs, lo_stats* st) {
+    if (!c || !T_curr || !T_matched || !T_rel_out || !inlier_ratio || (n_curr > 0 && !curr) || (n_matched > 0 && !matched))
+        return LO_ERR_ARG;
+    if (n_curr > static_cast<size_t>(c->cfg.max_points)) { c->err = "n_curr exceeds max_points"; return LO_ERR_CAPACITY; }
+    LO_HIP(c, hipSetDevice(c->device));
+    int rc = kd_alloc(c);
+    if (rc != LO_OK) return rc;
+    // local map of the matched keyframe: its feature cloud in the world (transform_point_cloud, :60-64)
+    const lo::SE3f Tm = lo::se3_from12(T_matched);
+    std::vector<float> lmap(3 * std::max<size_t>(n_matched, 1));
+    if (n_matched > 0) lo::transform_points(Tm, matched, n_matched, lmap.data());
+    // the matched cloud's grid first without the kd visit order (building it is ~0.3 ms of host work per call and
+    // it only ranks exact distance ties that decide a query's five neighbours or their order, which keyframe
+    // centroids rarely produce); a solve that met one is rerun with the order (loop_solve)
+    const bool all = n_matched <= static_cast<size_t>(kKnnAllMax);     // (the clouds' pinned upload, curr included)
+    rc = all ? all_pairs_upload(c, c->lgrid, lmap.data(), n_matched, curr, n_curr)
+             : grid_build(c, c->lgrid, lmap.data(), n_matched, false, kLoopMinPerCell);
+    if (rc != LO_OK) return rc;
+    return loop_solve(c, curr, false, n_curr, T_curr, lmap.data(), n_matched, T_matched, T_rel_out, inlier_ratio, logs, st);
+}
+
+// The same solve on device-resident clouds: the matched cloud goes to the world and into the local map's layout on
+// the device (loop_map_from_device), the current cloud is copied device to device (or is c->d_pts already).
+int lo_icp_optimize_loop_dev(lo_ctx* c, const float* d_curr, size_t n_curr, const float T_curr[12], const float* d_matched,
+                             size_t n_matched, const float T_matched[12], float T_rel_out[12], float* inlier_ratio,
+                             lo_iter_log* logs, lo_stats* st) {
+    if (!c || !T_curr || !T_matched || !T_rel_out || !inlier_ratio || (n_curr > 0 && !d_curr) ||
+        (n_matched > 0 && !d_matched))
+        return LO_ERR_ARG;
+    if (n_curr > static_cast<size_t>(c->cfg.max_points)) { c->err = "n_curr exceeds max_points"; return LO_ERR_CAPACITY; }
+    LO_HIP(c, hipSetDevice(c->device));
+    int rc = kd_alloc(c);
+    if (rc != LO_OK) return rc;
+    rc = loop_map_from_device(c, c->lgrid, d_matched, n_matched, T_matched, kLoopMinPerCell);
+    if (rc != LO_OK) return rc;
+    return loop_solve(c, d_curr, true, n_curr, T_curr, nullptr, n_matched, T_matched, T_rel_out, inlier_ratio, logs, st);
 }
 
 // ---------------------------------------------------------------- device preprocessing + optimize

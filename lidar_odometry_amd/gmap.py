@@ -104,6 +104,15 @@ class GlobalMapBuilder:
         """The context's last device-filtered scan (optimize_raw / voxel_filter) as the keyframe's cloud."""
         self._check(self._L.lo_gmap_add_from_scan(self._h, int(keyframe_id)))
 
+    def keyframe_points(self, index: int):
+        """(keyframe id, device pointer as int, count) of keyframe ``index`` (insertion order) inside the arena; no
+        copy, valid until clear / close.  IndexError past the end."""
+        kid, p, n = C.c_int64(0), C.c_void_p(0), C.c_size_t(0)
+        if not 0 <= int(index) < len(self):
+            raise IndexError(f"keyframe index {index} out of range ({len(self)} keyframes)")
+        self._check(self._L.lo_gmap_keyframe_points(self._h, int(index), C.byref(kid), C.byref(p), C.byref(n)))
+        return int(kid.value), int(p.value or 0), int(n.value)
+
     def build(self, poses, voxel_size: float) -> np.ndarray:
         """The map at these keyframe poses (one per keyframe, insertion order) -> (M, 3) float32; voxel_size <= 0:
         the transformed concatenation.  An empty builder gives a (0, 3) array (the reference's ``false``)."""

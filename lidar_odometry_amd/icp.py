@@ -296,6 +296,32 @@ class IterativeClosestPointOptimizer:
         conv = bool(st.converged)
         return rc == _lib.LO_OK, (pose34(Tr) if conv else None), (inl.value if conv else None)
 
+    def optimize_loop_dev(self, curr, curr_pose, matched, matched_pose):
+        """lo_icp_optimize_loop_dev: optimize_loop on device-resident clouds.  curr / matched: (N, 3) float32 device
+        tensors (``data_ptr()``), or (device pointer as int, count) pairs -- e.g. ``GlobalMapBuilder.keyframe_points``.
+        Same return values as ``optimize_loop`` and bit-identical to it for equal inputs."""
+        def dev(x):
+            if hasattr(x, "data_ptr"):
+                if not getattr(x, "is_cuda", False) or x.dim() != 2 or x.shape[1] != 3 or str(x.dtype) != "torch.float32":
+                    raise ValueError("device points must be an (N, 3) float32 device tensor")
+                x = x.contiguous()
+                return x, int(x.data_ptr()), int(x.shape[0])
+            ptr, n = x
+            return None, int(ptr), int(n)
+        kc, pc, nc = dev(curr)
+        km, pm, nm = dev(matched)
+        Tc, Tm = _as_pose(curr_pose), _as_pose(matched_pose)
+        Tr = np.zeros(12, np.float32)
+        inl = C.c_float(0.0)
+        logs = (LoIterLog * _lib.LO_MAX_ITERS)()
+        st = LoStats()
+        rc = self._check(lib().lo_icp_optimize_loop_dev(self._ctx, C.c_void_p(pc), nc, _fptr(Tc), C.c_void_p(pm), nm,
+                                                        _fptr(Tm), _fptr(Tr), C.byref(inl), logs, C.byref(st)))
+        del kc, km
+        self._record(st, logs)
+        conv = bool(st.converged)
+        return rc == _lib.LO_OK, (pose34(Tr) if conv else None), (inl.value if conv else None)
+
     def filtered_points(self) -> np.ndarray:
         """Feature cloud of the last device-filtered scan (for the keyframe map update)."""
         n = self._check(lib().lo_filtered_points(self._ctx, None, 0))

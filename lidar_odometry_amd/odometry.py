@@ -1,15 +1,15 @@
-"""Frame loop around the ICP step (Estimator::process_frame without loop closure / PGO), C++ in liblo_icp.so
-(lo_odometry.cpp, include/lo_odometry.h): device voxel filter + device GN ICP per frame, SE3f bookkeeping,
-keyframe map updates."""
+"""Frame loop around the ICP step (Estimator::process_frame; loop closure / PGO opt-in through
+``enable_loop_closure``), C++ in liblo_icp.so (lo_odometry.cpp, include/lo_odometry.h): device voxel filter + device
+GN ICP per frame, SE3f bookkeeping, keyframe map updates."""
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 import numpy as np
 
 from . import _lib
-from ._lib import LoOdomConfig, LoOdomFrame, lib
+from ._lib import LO_INSUFFICIENT, LoLoopConfig, LoLoopEvent, LoOdomConfig, LoOdomFrame, lib
 
 
 @dataclass
@@ -21,6 +21,54 @@ class FrameInfo:
     n_corr: int
     device_ms: float
     map_ms: float
+
+
+@dataclass
+class LoopConfig:
+    """lo_loop_config (defaults: the reference's ConfigUtils.h:117-134)."""
+    similarity_threshold: float = 0.3
+    min_keyframe_gap: int = 50
+    max_search_distance: float = 10.0
+    cooldown_keyframes: int = 50
+    min_inlier_ratio: float = 0.3
+    odom_trans_noise: float = 0.5
+    odom_rot_noise: float = 0.5
+    loop_trans_noise: float = 1.0
+    loop_rot_noise: float = 1.0
+    max_keyframes: int = 4096
+    max_points: int = 1 << 22
+
+    def to_c(self) -> LoLoopConfig:
+        c = LoLoopConfig()
+        lib().lo_loop_config_default(C.byref(c))
+        c.iris.similarity_threshold = float(self.similarity_threshold)
+        c.iris.min_keyframe_gap = int(self.min_keyframe_gap)
+        c.iris.max_search_distance = float(self.max_search_distance)
+        c.cooldown_keyframes = int(self.cooldown_keyframes)
+        c.min_inlier_ratio = float(self.min_inlier_ratio)
+        c.odom_trans_noise, c.odom_rot_noise = float(self.odom_trans_noise), float(self.odom_rot_noise)
+        c.loop_trans_noise, c.loop_rot_noise = float(self.loop_trans_noise), float(self.loop_rot_noise)
+        c.max_keyframes, c.max_points = int(self.max_keyframes), int(self.max_points)
+        return c
+
+
+@dataclass
+class LoopEvent:
+    """lo_loop_event: the last keyframe's loop attempt."""
+    keyframe_id: int
+    queried: bool
+    candidate_id: int
+    candidate_distance: float
+    candidate_bias: int
+    icp_status: int
+    icp_iterations: int
+    inlier_ratio: float
+    accepted: bool
+    pgo_converged: bool
+    pgo_iterations: int
+    correction_translation: float
+    correction_angle: float
+    ms: dict = field(default_factory=dict)       # detect / icp / pgo / map, host wall time
 
 
 class LidarOdometry:
@@ -76,6 +124,52 @@ class LidarOdometry:
         return T.reshape(3, 4), FrameInfo(info.status, bool(info.keyframe), info.icp_iterations, info.n_filtered,
                                           info.n_corr, info.device_ms, info.map_ms)
 
+    def _checked(self, rc):
+        if rc < 0:
+            raise RuntimeError(f"lo_odom error {rc}: {lib().lo_odom_last_error(self._o).decode()}")
+        return rc
+
+    def enable_loop_closure(self, config: LoopConfig | None = None) -> None:
+        """Close loops inside ``process`` (lo_odom_enable_loop_closure); before the first frame."""
+        c = (config or LoopConfig()).to_c()
+        self._checked(lib().lo_odom_enable_loop_closure(self._o, C.byref(c)))
+
+    @property
+    def last_loop(self) -> LoopEvent:
+        e = LoLoopEvent()
+        self._checked(lib().lo_odom_last_loop(self._o, C.byref(e)))
+        return LoopEvent(e.keyframe_id, bool(e.queried), e.candidate_id, e.candidate_distance, e.candidate_bias,
+                         e.icp_status, e.icp_iterations, e.inlier_ratio, bool(e.accepted), bool(e.pgo_converged),
+                         e.pgo_iterations, e.correction_translation, e.correction_angle,
+                         {"detect": e.detect_ms, "icp": e.icp_ms, "pgo": e.pgo_ms, "map": e.map_ms})
+
+    @property
+    def loop_count(self) -> int:
+        return int(lib().lo_odom_loop_count(self._o))
+
+    def keyframe_poses(self):
+        """(ids (K,) int32, current -- loop-corrected -- keyframe poses (K, 3, 4) float32)."""
+        n = int(lib().lo_odom_keyframe_poses(self._o, None, None, 0))
+        ids = np.zeros(max(n, 1), np.int32)
+        P = np.zeros((max(n, 1), 12), np.float32)
+        lib().lo_odom_keyframe_poses(self._o, ids.ctypes.data_as(C.POINTER(C.c_int)),
+                                     P.ctypes.data_as(C.POINTER(C.c_float)), n)
+        return ids[:n], P[:n].reshape(n, 3, 4)
+
+    def build_map(self, voxel_size: float) -> np.ndarray:
+        """The stored keyframe clouds at the current keyframe poses, voxel-grid filtered (lo_gmap_build) -> (M, 3)."""
+        n = C.c_size_t(0)
+        rc = self._checked(lib().lo_odom_build_map(self._o, float(voxel_size), C.byref(n)))
+        if rc == LO_INSUFFICIENT:
+            return np.zeros((0, 3), np.float32)
+        out = np.zeros((max(n.value, 1), 3), np.float32)
+        k = self._checked(lib().lo_odom_map_points(self._o, out.ctypes.data_as(C.POINTER(C.c_float)), n.value))
+        return out[:k]
+
+    def save_map_ply(self, path, voxel_size: float) -> None:
+        """Estimator::save_map_to_ply: build_map, then the PLY file."""
+        self._checked(lib().lo_odom_save_map_ply(self._o, str(path).encode(), float(voxel_size)))
+
     def flush(self):
         """Wait for the last keyframe's map update; raise if it overflowed the device map (lo_odom_flush)."""
         rc = lib().lo_odom_flush(self._o)
@@ -91,4 +185,4 @@ class LidarOdometry:
         return int(lib().lo_odom_map_surfels(self._o))
 
 
-__all__ = ["LidarOdometry", "FrameInfo", "_lib"]
+__all__ = ["LidarOdometry", "FrameInfo", "LoopConfig", "LoopEvent", "_lib"]
