@@ -4,9 +4,14 @@
  * (lo_odom_enable_loop_closure, below) and off in all odometry parity runs; without it the loop is:
  *   preprocess_frame (:561-589)            -> device FastVoxelFilter (lo_icp_optimize_raw)
  *   first frame (:235-269)                 -> pose = initial pose, create_keyframe
- *   guess = prev_pose * velocity (:154)    -> SE3f product with SO3 re-projection (MathUtils.h:144-147)
+ *   guess = previous_frame->get_pose() * velocity (:154)
+ *                                          -> SE3f product with SO3 re-projection (MathUtils.h:144-147).  get_pose()
+ *                                             (LidarFrame.cpp:113-128) is the stored pose only for a keyframe; for any
+ *                                             other frame it is last_keyframe_pose * relative_pose, recomposed through
+ *                                             two more re-projections (relative_pose = last_keyframe_pose^-1 * pose,
+ *                                             :186-191), so it is not the stored pose to the bit
  *   estimate_motion_dual_frame (:271-320) -> lo_icp_optimize_raw on the device map; failure keeps the guess
- *   velocity = prev^-1 * pose (:177)
+ *   velocity = previous_frame->get_pose()^-1 * pose (:177), the same recomposed previous pose
  *   should_create_keyframe (:349-368)      -> |dt| > keyframe_distance or |Log(R_kf^-1 R)| > keyframe_rotation
  *   create_keyframe (:370-530)             -> VoxelMap::UpdateVoxelMap(world cloud, position, 1.2 * max_range):
  *                                             surfel mode: the device-resident map (lo_devmap_update_from_scan,
@@ -44,6 +49,8 @@ typedef struct {
     int    n_corr;
     double device_ms;              /* preprocessing + ICP on the device (HIP events) */
     double map_ms;                 /* keyframe map update (host wall time: enqueue only with the device map), 0 otherwise */
+    float  guess[12];              /* debug: the guess of :154 this frame started from (row-major 3x4), before the
+                                      re-projection of :288; the returned pose for the first frame and the early return */
 } lo_odom_frame;
 
 typedef struct lo_odometry lo_odometry;
@@ -80,7 +87,7 @@ size_t        lo_odom_map_surfels(const lo_odometry* o);
  *
  * At every keyframe, after the map update: the feature cloud is stored (lo_gmap_add_from_scan), the pose graph is
  * extended (first keyframe: prior; later: odometry factor with relative = prev_keyframe_pose^-1 * pose, SE3f algebra,
- * the previous keyframe's CURRENT pose), and when keyframe_id - last_successful_loop_keyframe >= cooldown_keyframes
+ * the previous keyframe's CURRENT pose, its rotation normalised and re-projected as Estimator.cpp:385-390 does), and when keyframe_id - last_successful_loop_keyframe >= cooldown_keyframes
  * (that counter starts at -1, Estimator.cpp:38) the detector is queried with the device scan, THEN the keyframe is
  * added to it.  The reference adds first and queries afterwards; the order is equivalent because a database entry
  * closer than min_keyframe_gap ids -- the keyframe itself included -- is skipped by the selection, for every
@@ -128,6 +135,8 @@ typedef struct lo_loop_event {
     float  correction_translation;   /* |t| of the last keyframe's correction, m */
     float  correction_angle;         /* |Log(R)| of it, rad */
     double detect_ms, icp_ms, pgo_ms, map_ms;   /* host wall time of the four stages */
+    float  odom_edge[12];            /* debug: the odometry edge handed to the pose graph at this keyframe (row-major
+                                        3x4; identity for keyframe 0, which gets the prior instead) */
 } lo_loop_event;
 
 void      lo_loop_config_default(lo_loop_config* cfg);

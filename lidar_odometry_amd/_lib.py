@@ -96,7 +96,7 @@ class LoOdomConfig(C.Structure):
 
 class LoOdomFrame(C.Structure):
     _fields_ = [("status", C.c_int), ("keyframe", C.c_int), ("icp_iterations", C.c_int), ("n_filtered", C.c_int),
-                ("n_corr", C.c_int), ("device_ms", C.c_double), ("map_ms", C.c_double)]
+                ("n_corr", C.c_int), ("device_ms", C.c_double), ("map_ms", C.c_double), ("guess", C.c_float * 12)]
 
 
 class LoIrisConfig(C.Structure):
@@ -120,7 +120,7 @@ class LoLoopEvent(C.Structure):
                 ("icp_iterations", C.c_int), ("inlier_ratio", C.c_float), ("accepted", C.c_int),
                 ("pgo_converged", C.c_int), ("pgo_iterations", C.c_int), ("correction_translation", C.c_float),
                 ("correction_angle", C.c_float), ("detect_ms", C.c_double), ("icp_ms", C.c_double),
-                ("pgo_ms", C.c_double), ("map_ms", C.c_double)]
+                ("pgo_ms", C.c_double), ("map_ms", C.c_double), ("odom_edge", C.c_float * 12)]
 
 
 _lib = None

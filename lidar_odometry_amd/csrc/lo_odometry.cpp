@@ -1,6 +1,7 @@
 // lo_odometry.cpp — Estimator::process_frame, with opt-in loop closure / PGO (see include/lo_odometry.h), host C++
 // driving the device path: each frame is one lo_icp_optimize_raw call (device voxel filter + GN loop); the
-// pose bookkeeping uses the reference's SE3f algebra (lo_math.h); keyframes update the voxel map: in surfel mode the
+// pose bookkeeping is lo::FrameState (lo_frame_state.h: the reference's frame objects, flattened, on its SE3f algebra of
+// lo_math.h) -- this file keeps no pose of its own; keyframes update the voxel map: in surfel mode the
 // device-resident map (lo_devmap: the filtered scan never leaves the device, the context's table is patched in
 // place, no host sync), in KDTree mode the host VoxelMap (bit-identical UpdateVoxelMap restatement) + re-upload.
 #include <algorithm>
@@ -17,6 +18,7 @@
 #include "../../include/lo_odometry.h"
 #include "../../include/lo_pgo.h"
 #include "lo_ctx_internal.h"
+#include "lo_frame_state.h"
 #include "lo_math.h"
 
 using lo::SE3f;
@@ -28,7 +30,8 @@ struct lo_odometry {
     lo_devmap* dmap = nullptr;            // surfel mode (LO_HOST_MAP=1: the host map + patch sync instead)
     std::string err;
     bool initialized = false;
-    SE3f initial, prev, velocity, last_kf;
+    SE3f initial;
+    lo::FrameState fs;                    // previous frame, last keyframe, velocity, keyframe poses (loop closure)
     size_t keyframes = 0;
     std::vector<float> feat, world;
     // loop closure (lo_odom_enable_loop_closure); all null / empty otherwise
@@ -37,7 +40,6 @@ struct lo_odometry {
     lo_iris* iris = nullptr;
     lo_gmap* gmap = nullptr;
     lo_pgo* pgo = nullptr;
-    std::vector<SE3f> kf_poses;           // the keyframes' current (corrected) poses; keyframe id = index
     int last_loop_kf = -1;                // m_last_successful_loop_keyframe_id (Estimator.cpp:38)
     size_t loops = 0;
     lo_loop_event ev{};
@@ -67,25 +69,25 @@ static int loop_move_map(lo_odometry* o, const SE3f& corr) {
 
 // The loop bookkeeping of one new keyframe (id = its index) at `pose`, after its map update: create_keyframe's PGO /
 // detector part (:399-421, :496-517), then -- synchronously -- run_pgo_for_loop and the application of its result.
-static int loop_on_keyframe(lo_odometry* o, const SE3f& pose) {
-    const int id = static_cast<int>(o->kf_poses.size());
+static int loop_on_keyframe(lo_odometry* o, const SE3f& pose, const SE3f* edge) {
+    const std::vector<SE3f>& kf_poses = o->fs.kf_poses;      // this keyframe's pose is already its last entry
+    const int id = static_cast<int>(kf_poses.size()) - 1;
     lo_loop_event& ev = o->ev;
     ev = lo_loop_event{};
     ev.keyframe_id = id;
     ev.candidate_id = -1;
     ev.icp_status = LO_INSUFFICIENT;
+    lo::se3_to12(edge ? *edge : SE3f(), ev.odom_edge);
     float T[12];
     lo::se3_to12(pose, T);
     int rc = lo_gmap_add_from_scan(o->gmap, id);
     if (rc != LO_OK) { o->err = std::string("loop closure keyframe store: ") + lo_gmap_last_error(o->gmap); return rc; }
-    if (id == 0) {
+    if (!edge) {
         lo_pgo_add_first_keyframe(o->pgo, id, T);
-    } else {
-        float rel[12];
-        lo::se3_to12(lo::se3_mul(lo::se3_inv(o->kf_poses.back()), pose), rel);
-        lo_pgo_add_keyframe_with_odom(o->pgo, id - 1, id, T, rel, o->lcfg.odom_trans_noise, o->lcfg.odom_rot_noise);
+    } else {                                                 // the normalised relative pose (:385-390)
+        lo_pgo_add_keyframe_with_odom(o->pgo, id - 1, id, T, ev.odom_edge, o->lcfg.odom_trans_noise,
+                                      o->lcfg.odom_rot_noise);
     }
-    o->kf_poses.push_back(pose);
     const size_t n_curr = static_cast<size_t>(std::max<long long>(o->last_nf, 0));
     const float* d_curr = nullptr;
     const int* d_n = nullptr;
@@ -114,7 +116,7 @@ static int loop_on_keyframe(lo_odometry* o, const SE3f& pose) {
     if (rc != LO_OK) { o->err = lo_gmap_last_error(o->gmap); return rc; }
     if (n_m == 0 || n_curr == 0) return LO_OK;               // "Empty feature clouds for loop" (:989-995)
     float Tm[12], Trel[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    lo::se3_to12(o->kf_poses[mid], Tm);
+    lo::se3_to12(kf_poses[mid], Tm);
     lo_stats st{};
     float inl = 0.0f;
     const auto t1 = std::chrono::steady_clock::now();
@@ -127,27 +129,30 @@ static int loop_on_keyframe(lo_odometry* o, const SE3f& pose) {
     if (rc != LO_OK || inl < o->lcfg.min_inlier_ratio) return LO_OK;          // :1008-1020
     const SE3f corrected = lo::se3_mul(pose, lo::se3_from12(Trel));            // :1027
     float con[12];
-    lo::se3_to12(lo::se3_mul(lo::se3_inv(o->kf_poses[mid]), corrected), con);  // :1039
+    lo::se3_to12(lo::se3_mul(lo::se3_inv(kf_poses[mid]), corrected), con);  // :1039
     const auto t2 = std::chrono::steady_clock::now();
     const int ok = lo_pgo_add_loop_and_optimize(o->pgo, mid, id, con, o->lcfg.loop_trans_noise, o->lcfg.loop_rot_noise,
                                                 &ev.pgo_converged, &ev.pgo_iterations, nullptr);
     ev.pgo_ms = ms_since(t2);
     if (ok != 1) return LO_OK;                                                 // "PGO failed!" (:1080-1083)
-    // apply_pending_pgo_result_if_available, here and now: poses, map, previous-frame pose, cooldown
-    const SE3f before = o->kf_poses.back();
+    // apply_pending_pgo_result_if_available, here and now: poses, map, cooldown
+    const SE3f before = kf_poses.back();
+    std::vector<SE3f> opt(kf_poses);
     for (int k = 0; k <= id; ++k) {
         float P[12];
-        if (lo_pgo_get_optimized_pose(o->pgo, k, P) == 1) o->kf_poses[k] = lo::se3_from12(P);
+        if (lo_pgo_get_optimized_pose(o->pgo, k, P) == 1) opt[k] = lo::se3_from12(P);
     }
-    const SE3f corr = lo::se3_mul(o->kf_poses.back(), lo::se3_inv(before));    // :1121
+    o->fs.on_correction(opt.data(), opt.size());             // :1158-1175
+    const SE3f corr = lo::se3_mul(kf_poses.back(), lo::se3_inv(before));       // :1121
     ev.correction_translation = std::sqrt(lo::dot3e(corr.t[0], corr.t[1], corr.t[2], corr.t[0], corr.t[1], corr.t[2]));
     ev.correction_angle = lo::so3_log_norm(corr.R);
     const auto t3 = std::chrono::steady_clock::now();
     rc = loop_move_map(o, corr);
     ev.map_ms = ms_since(t3);
     if (rc != LO_OK) return rc;
-    o->prev = o->kf_poses.back();                            // m_previous_frame is this keyframe; m_velocity is kept;
-    o->last_loop_kf = id;                                    // m_last_keyframe_pose (o->last_kf) is NOT moved (:494)
+    // (m_previous_frame is this keyframe, so the next guess starts from its corrected pose; m_velocity is kept;
+    // m_last_keyframe_pose, FrameState::last_kf, is NOT moved (:494))
+    o->last_loop_kf = id;
     ++o->loops;
     ev.accepted = 1;
     return LO_OK;
@@ -163,7 +168,6 @@ static int create_keyframe(lo_odometry* o, const SE3f& pose, lo_odom_frame* info
         if (rc == LO_OK && !o->cfg.icp.use_surfel_correspondence)
             rc = lo_devmap_sync_points(o->dmap);         // RebuildKdTree (Estimator.cpp:460-462) on the device
         if (rc != LO_OK) { o->err = lo_devmap_last_error(o->dmap); return rc; }
-        o->last_kf = pose;
         ++o->keyframes;
         // the map's error bits (an update that overflowed a capacity aborted; tracking would go on against a stale
         // map): copied back behind the update without a sync, read after the next frame's ICP (lo_odom_process)
@@ -175,7 +179,9 @@ static int create_keyframe(lo_odometry* o, const SE3f& pose, lo_odom_frame* info
             info->keyframe = 1;
             info->map_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         }
-        return o->loop_on ? loop_on_keyframe(o, pose) : LO_OK;
+        SE3f edge;
+        const bool has_edge = o->fs.on_keyframe(pose, &edge);
+        return o->loop_on ? loop_on_keyframe(o, pose, has_edge ? &edge : nullptr) : LO_OK;
     }
     const long long n = lo_filtered_points(o->icp, nullptr, 0);
     if (n < 0) { o->err = lo_last_error(o->icp); return static_cast<int>(n); }
@@ -187,13 +193,14 @@ static int create_keyframe(lo_odometry* o, const SE3f& pose, lo_odom_frame* info
     int rc = lo_voxelmap_update(o->map, o->world.data(), static_cast<size_t>(n), sensor, o->cfg.max_range * 1.2, 1);
     if (rc == LO_OK) rc = lo_map_sync_voxelmap(o->icp, o->map, nullptr);                 // patch (+ RebuildKdTree)
     if (rc != LO_OK) { o->err = "keyframe map update failed"; return rc; }
-    o->last_kf = pose;
     ++o->keyframes;
     if (info) {
         info->keyframe = 1;
         info->map_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
-    return o->loop_on ? loop_on_keyframe(o, pose) : LO_OK;
+    SE3f edge;
+    const bool has_edge = o->fs.on_keyframe(pose, &edge);
+    return o->loop_on ? loop_on_keyframe(o, pose, has_edge ? &edge : nullptr) : LO_OK;
 }
 
 extern "C" {
@@ -271,8 +278,8 @@ int lo_odom_process(lo_odometry* o, const float* raw, size_t n, float T_out[12],
         if (nf < 0) { o->err = lo_last_error(o->icp); return static_cast<int>(nf); }
         fi->n_filtered = static_cast<int>(nf);
         o->last_nf = nf;
-        o->prev = o->initial;
-        o->velocity = SE3f();
+        o->fs.init(o->initial);
+        lo::se3_to12(o->initial, fi->guess);
         if (nf > 0) {
             const int rc = create_keyframe(o, o->initial, fi);
             if (rc != LO_OK) return rc;
@@ -285,11 +292,16 @@ int lo_odom_process(lo_odometry* o, const float* raw, size_t n, float T_out[12],
     if (o->keyframes == 0) {
         // the first frame filtered to nothing: the reference made no keyframe and every later frame returns at
         // "No keyframe available" (Estimator.cpp:140-144) without ICP, pose update or keyframe test
-        lo::se3_to12(o->prev, T_out);
+        lo::se3_to12(o->fs.prev_pose(), T_out);
+        std::memcpy(fi->guess, T_out, sizeof(fi->guess));
         fi->status = LO_OK;
         return LO_OK;
     }
-    const SE3f guess = lo::se3_mul(o->prev, o->velocity);                    // :154
+    // :154: m_previous_frame->get_pose() * m_velocity.  get_pose() is the stored pose only when the previous frame is a
+    // keyframe; otherwise it is recomposed from the last keyframe's pose and the frame's relative pose
+    // (LidarFrame.cpp:113-128; lo_frame_state.h), which is not the stored pose to the bit
+    const SE3f guess = o->fs.guess();
+    lo::se3_to12(guess, fi->guess);
     // estimate_motion_dual_frame hands optimize SE3f(guess.R, guess.t), i.e. SO3(R) re-projected (:284), and
     // wraps the result the same way (:308); on failure it returns the guess itself (:304-307)
     SE3f g_in = guess;
@@ -318,19 +330,10 @@ int lo_odom_process(lo_odometry* o, const float* raw, size_t n, float T_out[12],
         lo::so3_project_svd(r.R, pose.R);
     }
     lo::se3_to12(pose, p12);
-    o->velocity = lo::se3_mul(lo::se3_inv(o->prev), pose);                    // :177
-    o->prev = pose;
-    // should_create_keyframe (:349-368)
-    const float dt[3] = {pose.t[0] - o->last_kf.t[0], pose.t[1] - o->last_kf.t[1], pose.t[2] - o->last_kf.t[2]};
-    const float dist = std::sqrt(lo::dot3e(dt[0], dt[1], dt[2], dt[0], dt[1], dt[2]));
-    float Rki[3][3], Rkt[3][3], Rrel[3][3], Rrel_p[3][3];
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) Rkt[r][c] = o->last_kf.R[c][r];
-    lo::so3_project_svd(Rkt, Rki);                                                // SO3::Inverse -> SO3(R^T)
-    lo::mul33e(Rki, pose.R, Rrel);
-    lo::so3_project_svd(Rrel, Rrel_p);                                            // SO3::operator*
-    const double ang = lo::so3_log_norm(Rrel_p);
-    if (static_cast<double>(dist) > o->cfg.keyframe_distance || ang > o->cfg.keyframe_rotation) {
-        const int krc = create_keyframe(o, pose, fi);       // (a closed loop moves o->prev, not this frame's pose)
+    // :177 velocity = m_previous_frame->get_pose().Inverse() * pose (the same recomposed previous pose), :181-191 the
+    // frame's stored and relative pose, :198 should_create_keyframe (:349-368)
+    if (o->fs.commit(pose, o->cfg.keyframe_distance, o->cfg.keyframe_rotation)) {
+        const int krc = create_keyframe(o, pose, fi);       // (a closed loop moves the keyframe, not this frame's pose)
         if (krc != LO_OK) return krc;
     }
     std::memcpy(T_out, p12, sizeof(p12));
@@ -384,6 +387,7 @@ int lo_odom_enable_loop_closure(lo_odometry* o, const lo_loop_config* cfg) {
     o->ev.keyframe_id = -1;
     o->ev.candidate_id = -1;
     o->loop_on = true;
+    o->fs.keep_kf_poses = true;
     return LO_OK;
 }
 
@@ -398,10 +402,10 @@ size_t lo_odom_loop_count(const lo_odometry* o) { return o ? o->loops : 0; }
 
 size_t lo_odom_keyframe_poses(const lo_odometry* o, int* ids, float* poses, size_t cap) {
     if (!o) return 0;
-    const size_t n = o->kf_poses.size();
+    const size_t n = o->fs.kf_poses.size();
     for (size_t k = 0; k < n && k < cap; ++k) {
         if (ids) ids[k] = static_cast<int>(k);
-        if (poses) lo::se3_to12(o->kf_poses[k], poses + 12 * k);
+        if (poses) lo::se3_to12(o->fs.kf_poses[k], poses + 12 * k);
     }
     return n;
 }
@@ -409,9 +413,9 @@ size_t lo_odom_keyframe_poses(const lo_odometry* o, int* ids, float* poses, size
 int lo_odom_build_map(lo_odometry* o, float voxel_size, size_t* out_n) {
     if (!o) return LO_ERR_ARG;
     if (!o->loop_on) { o->err = "loop closure is not enabled"; return LO_ERR_STATE; }
-    std::vector<float> P(12 * std::max<size_t>(o->kf_poses.size(), 1));
-    for (size_t k = 0; k < o->kf_poses.size(); ++k) lo::se3_to12(o->kf_poses[k], P.data() + 12 * k);
-    const int rc = lo_gmap_build(o->gmap, P.data(), o->kf_poses.size(), voxel_size, out_n);
+    std::vector<float> P(12 * std::max<size_t>(o->fs.kf_poses.size(), 1));
+    for (size_t k = 0; k < o->fs.kf_poses.size(); ++k) lo::se3_to12(o->fs.kf_poses[k], P.data() + 12 * k);
+    const int rc = lo_gmap_build(o->gmap, P.data(), o->fs.kf_poses.size(), voxel_size, out_n);
     if (rc < 0) o->err = lo_gmap_last_error(o->gmap);
     return rc;
 }

@@ -21,6 +21,12 @@ class FrameInfo:
     n_corr: int
     device_ms: float
     map_ms: float
+    _guess: object = None                        # lo_odom_frame.guess as it came back (converted on demand)
+
+    @property
+    def guess(self) -> np.ndarray:
+        """(12,) float32: the guess this frame started from (debug output of lo_odom_process)."""
+        return np.array(self._guess[:], np.float32)
 
 
 @dataclass
@@ -69,6 +75,7 @@ class LoopEvent:
     correction_translation: float
     correction_angle: float
     ms: dict = field(default_factory=dict)       # detect / icp / pgo / map, host wall time
+    odom_edge: np.ndarray | None = None          # (12,) float32: the odometry edge handed to the pose graph (debug)
 
 
 class LidarOdometry:
@@ -122,7 +129,8 @@ class LidarOdometry:
         if rc < 0:
             raise RuntimeError(f"lo_odom_process error {rc}: {lib().lo_odom_last_error(self._o).decode()}")
         return T.reshape(3, 4), FrameInfo(info.status, bool(info.keyframe), info.icp_iterations, info.n_filtered,
-                                          info.n_corr, info.device_ms, info.map_ms)
+                                          info.n_corr, info.device_ms, info.map_ms,
+                                          info.guess)
 
     def _checked(self, rc):
         if rc < 0:
@@ -141,7 +149,8 @@ class LidarOdometry:
         return LoopEvent(e.keyframe_id, bool(e.queried), e.candidate_id, e.candidate_distance, e.candidate_bias,
                          e.icp_status, e.icp_iterations, e.inlier_ratio, bool(e.accepted), bool(e.pgo_converged),
                          e.pgo_iterations, e.correction_translation, e.correction_angle,
-                         {"detect": e.detect_ms, "icp": e.icp_ms, "pgo": e.pgo_ms, "map": e.map_ms})
+                         {"detect": e.detect_ms, "icp": e.icp_ms, "pgo": e.pgo_ms, "map": e.map_ms},
+                         np.array(e.odom_edge[:], np.float32))
 
     @property
     def loop_count(self) -> int:

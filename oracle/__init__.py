@@ -184,13 +184,24 @@ def keyframe_metrics(kf, pose):
 
 def odometry(raw_scans, stride=8, voxel=0.5, map_voxel=0.5, max_range=100.0, kf_dist=1.0, kf_rot=0.3, initial=None):
     """Estimator::process_frame without loop closure / PGO (Estimator.cpp:115-233), on the oracle primitives.
-    Returns (poses (n, 12) float32, keyframe flags)."""
+    Returns (poses (n, 12) float32, keyframe flags).
+
+    The previous frame's pose behind the guess (:154) and the velocity (:177) is LidarFrame::get_pose()
+    (LidarFrame.cpp:113-128): the stored pose when that frame is a keyframe (or there is no keyframe yet), otherwise
+    last_keyframe_pose * relative_pose with relative_pose = last_keyframe_pose^-1 * pose (:186-191) -- an inverse and
+    two products, each re-projecting its rotation, so not the stored pose to the bit."""
     I = np.eye(3, 4, dtype=np.float32).reshape(12)
     P0 = I if initial is None else np.ascontiguousarray(np.asarray(initial, np.float32)[:3, :4].reshape(12))
     m = VoxelMap(map_voxel, 3, 0.1, True)
     poses, kfs = [], []
-    prev = vel = last_kf = I
+    stored = vel = last_kf = rel = I           # previous frame: stored pose, relative pose; the last keyframe's pose
+    prev_is_kf = False
     n_kf = 0
+
+    def prev_pose():
+        if prev_is_kf or n_kf == 0:
+            return stored
+        return se3_compose(last_kf, rel)
     for k, raw in enumerate(raw_scans):
         pts = voxel_filter(raw, voxel, stride)
         kf = False
@@ -199,10 +210,11 @@ def odometry(raw_scans, stride=8, voxel=0.5, map_voxel=0.5, max_range=100.0, kf_
             kf = len(pts) > 0
         elif n_kf == 0:
             # empty first frame: no keyframe was made, so every later frame returns early (Estimator.cpp:140-144)
-            poses.append(np.asarray(prev, np.float32).reshape(12))
+            poses.append(np.asarray(prev_pose(), np.float32).reshape(12))
             kfs.append(False)
             continue
         else:
+            prev = prev_pose()
             guess = se3_compose(prev, vel)
             g_in = guess.copy().reshape(3, 4)
             g_in[:, :3] = so3_normalize(g_in[:, :3].reshape(9)).reshape(3, 3)
@@ -214,9 +226,10 @@ def odometry(raw_scans, stride=8, voxel=0.5, map_voxel=0.5, max_range=100.0, kf_
             else:
                 pose = guess
             vel = se3_compose(se3_inverse(prev), pose)
+            rel = se3_compose(se3_inverse(last_kf), pose)
             d, a = keyframe_metrics(last_kf, pose)
             kf = d > kf_dist or a > kf_rot
-        prev = pose
+        stored, prev_is_kf = pose, kf
         if kf:
             n_kf += 1
             w = transform_points(pts, pose)

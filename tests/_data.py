@@ -44,6 +44,17 @@ def kitti_scan(i: int, n_frames: int = 40):
 
 
 @functools.lru_cache(maxsize=None)
+def ramp_seq(n_frames: int = 12):
+    """The frame-loop tests' sequence: the vehicle starts from rest, so the identity velocity prior at frame 1 holds."""
+    return synth.KittiLikeSequence(seed=7, n_frames=n_frames, ramp_s=2.0)
+
+
+@functools.lru_cache(maxsize=None)
+def ramp_scan(i: int, n_frames: int = 12):
+    return ramp_seq(n_frames).scan(i)
+
+
+@functools.lru_cache(maxsize=None)
 def kitti_map(last_kf: int = 20, n_frames: int = 40, voxel: float = 0.5, stride: int = 8):
     """Oracle VoxelMap fed with keyframes 0, 2, ..., last_kf at ground-truth poses (kitti.yaml params)."""
     seq = kitti_seq(n_frames)

@@ -1,10 +1,9 @@
 """The frame loop with loop closure, assembled by hand from the library's public pieces (test infrastructure for
 tests/test_gpu_slam.py): lo_icp_optimize_raw, lo_devmap_update_from_scan, IrisLoopDetector, GlobalMapBuilder,
-lo_icp_optimize_loop on HOST clouds, PoseGraphOptimizer and lo_devmap_apply_transform, with the bookkeeping of
-include/lo_odometry.h kept here in numpy.  The SE3f products (guess, velocity, relative pose, corrected pose,
-constraint, correction) and the keyframe test go through the oracle's restatements of the reference's SE3f algebra
-(oracle.se3_compose / se3_inverse / so3_normalize / keyframe_metrics), which the odometry parity tests already hold
-equal to the library's lo_math.h.
+lo_icp_optimize_loop on HOST clouds, PoseGraphOptimizer and lo_devmap_apply_transform.  The pose bookkeeping (previous
+frame, guess, velocity, keyframe test, odometry edge, what a correction moves) is the frame-object model of
+tests/_frame_ref.py, driven here by the library's ICP; the loop's own SE3f products (corrected pose, constraint,
+correction) go through the oracle's restatements of the reference's SE3f algebra (oracle.se3_compose / se3_inverse).
 
 Deliberately different from lo_odom's own path where the library offers a second one: keyframe clouds are host copies
 (the detector, the loop ICP and the map builder read them from the host), so the device-resident path is checked
@@ -20,6 +19,7 @@ from lidar_odometry_amd import (GlobalMapBuilder, ICPConfig, IrisLoopDetector, I
                                 LoopClosureConfig, _lib)
 from lidar_odometry_amd.pgo import PoseGraphOptimizer
 from lidar_odometry_amd.voxelmap import DeviceVoxelMap
+from tests import _frame_ref
 
 I12 = np.eye(3, 4, dtype=np.float32).reshape(12)
 STRIDE, VOXEL, MAX_RANGE, KF_DIST, KF_ROT = 8, 0.5, 100.0, 1.0, 0.3      # lo_odom_config_default_kitti
@@ -27,12 +27,6 @@ STRIDE, VOXEL, MAX_RANGE, KF_DIST, KF_ROT = 8, 0.5, 100.0, 1.0, 0.3      # lo_od
 
 def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
-
-
-def _normalized(T12):
-    T = np.asarray(T12, np.float32).reshape(3, 4).copy()
-    T[:, :3] = oracle.so3_normalize(T[:, :3].reshape(9)).reshape(3, 3)
-    return T.reshape(12)
 
 
 @dataclass
@@ -44,6 +38,8 @@ class Run:
     kf_poses: list = field(default_factory=list)       # current (corrected)
     map: np.ndarray | None = None
     loops: int = 0
+    guesses: list = field(default_factory=list)        # per frame: the model's guess (None for the first frame)
+    odom_edges: list = field(default_factory=list)     # per keyframe: the edge handed to the pose graph (None for the first)
 
 
 def run(scans, cfg, map_voxel: float, kdtree: bool = False, max_points: int = 1 << 15) -> Run:
@@ -57,35 +53,31 @@ def run(scans, cfg, map_voxel: float, kdtree: bool = False, max_points: int = 1 
     pgo = PoseGraphOptimizer()
     out = Run()
     clouds = []
-    prev = vel = last_kf = I12
+    est = _frame_ref.Estimator(KF_DIST, KF_ROT)
     last_loop = -1
     try:
         for k, raw in enumerate(scans):
             raw = np.ascontiguousarray(raw, np.float32).reshape(-1, 3)
-            status = _lib.LO_OK
-            if k == 0:
-                pose = I12
-                kf = len(icp.voxel_filter(raw, VOXEL, STRIDE)) > 0
-            else:
-                guess = oracle.se3_compose(prev, vel)
-                g_in = _normalized(guess)
+            state = {"status": _lib.LO_OK}
+
+            def lib_icp(_points, guess12, raw=raw, state=state):
                 To = np.zeros(12, np.float32)
                 st = _lib.LoStats()
                 logs = (_lib.LoIterLog * _lib.LO_MAX_ITERS)()
-                status = L.lo_icp_optimize_raw(icp.ctx, _fp(raw), len(raw), STRIDE, VOXEL, _fp(g_in), _fp(To), logs,
-                                               C.byref(st))
-                assert status >= 0, status
-                pose = _normalized(To) if status == _lib.LO_OK else guess
-                vel = oracle.se3_compose(oracle.se3_inverse(prev), pose)
-                d, a = oracle.keyframe_metrics(last_kf, pose)
-                kf = d > KF_DIST or a > KF_ROT
-            prev = pose
+                g = np.ascontiguousarray(guess12, np.float32)
+                state["status"] = L.lo_icp_optimize_raw(icp.ctx, _fp(raw), len(raw), STRIDE, VOXEL, _fp(g), _fp(To), logs,
+                                                        C.byref(st))
+                assert state["status"] >= 0, state["status"]
+                return state["status"] == _lib.LO_OK, To
+
+            # (the model looks at the points of the first frame only: an empty feature cloud makes no keyframe)
+            pose, kf, _ = est.process(icp.voxel_filter(raw, VOXEL, STRIDE) if k == 0 else raw, lib_icp)
+            status = state["status"]
             if kf:
                 pose = np.ascontiguousarray(pose, np.float32)
                 assert L.lo_devmap_update_from_scan(dm._h, _fp(pose), 1.2 * MAX_RANGE) == _lib.LO_OK
                 if kdtree:
                     assert L.lo_devmap_sync_points(dm._h) == _lib.LO_OK
-                last_kf = pose
                 # ---- the loop bookkeeping of include/lo_odometry.h
                 kid = len(out.kf_poses)
                 cloud = icp.filtered_points()
@@ -94,7 +86,7 @@ def run(scans, cfg, map_voxel: float, kdtree: bool = False, max_points: int = 1 
                 if kid == 0:
                     pgo.add_first_keyframe(kid, pose)
                 else:
-                    rel = oracle.se3_compose(oracle.se3_inverse(out.kf_poses[-1]), pose)
+                    rel = est.odom_edges[-1]
                     pgo.add_keyframe_with_odom(kid - 1, kid, pose, rel, cfg.odom_trans_noise, cfg.odom_rot_noise)
                 out.kf_poses.append(pose.copy())
                 pos = pose.reshape(3, 4)[:, 3].copy()
@@ -120,7 +112,7 @@ def run(scans, cfg, map_voxel: float, kdtree: bool = False, max_points: int = 1 
                             dm.apply_transform(corr)
                             if kdtree:
                                 assert L.lo_devmap_sync_points(dm._h) == _lib.LO_OK
-                            prev = out.kf_poses[-1]
+                            est.apply_correction(out.kf_poses)
                             last_loop = kid
                             out.loops += 1
                             ev[6] = True
@@ -128,6 +120,8 @@ def run(scans, cfg, map_voxel: float, kdtree: bool = False, max_points: int = 1 
             out.poses.append(np.asarray(pose, np.float32).reshape(12).copy())
             out.status.append(status)
             out.keyframe.append(bool(kf))
+        out.guesses = list(est.guesses)
+        out.odom_edges = list(est.odom_edges)
         out.map = gm.build(np.stack(out.kf_poses), map_voxel) if out.kf_poses else np.zeros((0, 3), np.float32)
         return out
     finally:

@@ -78,6 +78,38 @@ def test_odometry_exact_mode_is_bitwise():
                                       np.asarray(ref[k], np.float32).view(np.uint32), err_msg=f"frame {k}")
 
 
+@pytest.fixture(scope="module")
+def model_scans():
+    n = 12
+    return [_data.ramp_scan(k, n) for k in range(n)], _data.ramp_seq(n).poses[0]
+
+
+@pytest.mark.parametrize("kdtree", [False, True], ids=["surfel", "kdtree"])
+def test_exact_frame_loop_equals_the_frame_model(model_scans, kdtree):
+    """lo_odom_process in exact mode against the model of the reference's frame objects (tests/_frame_ref.py: the
+    previous frame read through LidarFrame::get_pose()), driven by the oracle's ICP on the oracle's map: poses as bit
+    patterns, keyframe flags, and the guess each frame started from."""
+    from lidar_odometry_amd.odometry import LidarOdometry
+    from tests import _frame_ref
+    raws, T0 = model_scans
+    est, poses, flags = _frame_ref.run_oracle(raws, initial=T0, kdtree=kdtree)
+    non_kf, differ = _frame_ref.input_conditions(est)           # conditions on the model's run alone
+    assert len(non_kf) >= 3 and len(differ) >= 1, (non_kf, differ)
+    assert sum(flags) >= 2
+    od = LidarOdometry(initial_pose=T0, exact=True, use_surfel_correspondence=not kdtree)
+    try:
+        out = [od.process(r) for r in raws]
+    finally:
+        od.close()
+    assert [i.keyframe for _, i in out] == flags
+    for k, (T, info) in enumerate(out):
+        np.testing.assert_array_equal(np.asarray(T, np.float32).reshape(12).view(np.uint32), poses[k].view(np.uint32),
+                                      err_msg=f"pose, frame {k}")
+        if k:
+            np.testing.assert_array_equal(info.guess.view(np.uint32), est.guesses[k].view(np.uint32),
+                                          err_msg=f"guess, frame {k}")
+
+
 def test_odometry_tracks_ground_truth(runs):
     got, infos, _, _, _, seq = runs
     err = [np.linalg.norm(got[k].reshape(3, 4)[:, 3] - seq.poses[k][:3, 3]) for k in range(N_FRAMES)]

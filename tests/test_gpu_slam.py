@@ -50,18 +50,20 @@ def _odom_run(scans, cfg, kdtree=False, after=None):
     try:
         if cfg is not None:
             o.enable_loop_closure(cfg)
-        poses, status, flags, events = [], [], [], []
+        poses, status, flags, events, guesses, edges = [], [], [], [], [], []
         for raw in scans:
             T, info = o.process(raw)
             poses.append(T.reshape(12).copy())
             status.append(info.status)
             flags.append(info.keyframe)
+            guesses.append(info.guess)
             if info.keyframe and cfg is not None:
                 e = o.last_loop
+                edges.append(e.odom_edge)
                 events.append((e.keyframe_id, e.queried, e.candidate_id, np.float32(e.candidate_distance),
                                e.candidate_bias, np.float32(e.inlier_ratio), e.accepted))
         o.flush()
-        out = {"poses": poses, "status": status, "flags": flags, "events": events}
+        out = {"poses": poses, "status": status, "flags": flags, "events": events, "guesses": guesses, "edges": edges}
         if cfg is not None:
             out["loops"] = o.loop_count
             out["kf_ids"], out["kf_poses"] = o.keyframe_poses()
@@ -107,6 +109,27 @@ def test_composition_equality(ref_run, odom_run):
     np.testing.assert_array_equal(_bits(odom_run["kf_poses"]), _bits(np.stack(ref_run.kf_poses)))
     np.testing.assert_array_equal(_bits(odom_run["map"]), _bits(ref_run.map))
     assert len(ref_run.map) > 1000
+
+
+def test_odometry_edges_and_guesses_equal_the_frame_model(ref_run, odom_run):
+    """What lo_odom hands to lo_pgo as the odometry edge of every keyframe (lo_loop_event.odom_edge) is the frame-object
+    model's normalised relative pose (Estimator.cpp:385-390), bit for bit, and every frame -- the three after the first
+    accepted correction in particular -- starts from the model's guess (lo_odom_frame.guess): the previous frame read
+    through get_pose(), i.e. through the corrected keyframe."""
+    assert ref_run.loops >= 1                                   # (conditions on the model's run)
+    first_kf = next(e[0] for e in ref_run.events if e[6])
+    f = [k for k, kf in enumerate(ref_run.keyframe) if kf][first_kf]
+    assert f + 3 < len(ref_run.poses)
+    assert any(not kf for kf in ref_run.keyframe[f + 1:f + 4])  # a non-keyframe hangs off the corrected keyframe
+    assert ref_run.odom_edges[0] is None and len(ref_run.odom_edges) == len(odom_run["edges"]) >= 3
+    np.testing.assert_array_equal(_bits(odom_run["edges"][0]), _bits(np.eye(3, 4)))
+    for j in range(1, len(ref_run.odom_edges)):
+        np.testing.assert_array_equal(_bits(odom_run["edges"][j]), _bits(ref_run.odom_edges[j]), err_msg=f"keyframe {j}")
+    assert ref_run.guesses[0] is None
+    for k in list(range(f + 1, f + 4)) + list(range(1, len(ref_run.guesses))):
+        np.testing.assert_array_equal(_bits(odom_run["guesses"][k]), _bits(ref_run.guesses[k]), err_msg=f"frame {k}")
+    # the guess behind frame f + 1 starts from the CORRECTED keyframe pose, which the frame's returned pose is not
+    assert not np.array_equal(_bits(odom_run["kf_poses"][first_kf]), _bits(odom_run["poses"][f])) or ref_run.loops > 1
 
 
 def test_loop_closure_off_is_the_plain_frame_loop(scans, odom_run):
