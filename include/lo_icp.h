@@ -269,6 +269,32 @@ int lo_batch_result(lo_batch* b, lo_batch_rec* out, double* gpu_ms);
 int lo_batch_bench_correspond(lo_batch* b, int reps, float* avg_ms);
 /* Host points in, records out (H2D of every scan on the batch stream, enqueue, wait). */
 int lo_batch_optimize(lo_batch* b, const float* const* pts, const size_t* n, const float* T_init, lo_batch_rec* out);
+/* Raw scans into a batch: Estimator::preprocess_frame (Estimator.cpp:561-588), i.e. FastVoxelFilter::filter
+ * (VoxelMap.h:73-104), for every job in one set of batched launches on the batch stream (five launches for the whole
+ * batch instead of five per context).  Each job's output is bit-identical to lo_voxel_filter_gpu on the same input.
+ *
+ * lo_batch_filter_raw: d_raw[j]: device pointer or the device
+ * alias of pinned host memory (AoS float3), n_raw[j] points (0 allowed: count 0).  Job j's output is its
+ * context's device-filtered scan (as after lo_voxel_filter_gpu: lo_filtered_points etc. see it) and n_out[j]
+ * its count.  Synchronous: returns after the counts are on the host.  The contexts must be idle, as for every batch
+ * call.  Errors (lo_batch_last_error; nothing is enqueued): LO_ERR_ARG for a null array, stride < 1,
+ * !(voxel_size > 0) or a null d_raw[j] with n_raw[j] > 0; LO_ERR_CAPACITY when a job's ceil(n_raw / stride) exceeds
+ * its context's max_points; LO_ERR_STATE while a batch is in flight.  Afterwards
+ * lo_batch_optimize_async(b, NULL, counts, T_init) optimizes the filtered clouds. */
+int lo_batch_filter_raw(lo_batch* b, const float* const* d_raw, const size_t* n_raw, int stride, float voxel_size,
+                        size_t* n_out);
+/* The same with host scans: pinned memory (lo_host_alloc) is read in place, pageable memory staged in device memory
+ * on the batch stream (as lo_icp_optimize_raw stages a scan). */
+int lo_batch_filter_raw_host(lo_batch* b, const float* const* raw, const size_t* n_raw, int stride, float voxel_size,
+                             size_t* n_out);
+/* Device time of the last batched filter's launches in ms (HIP events on the batch stream); -1 before the first. */
+double lo_batch_filter_ms(const lo_batch* b);
+/* Host raw scans in, records out: stage (pinned memory is read in place, as lo_icp_optimize_raw), filter,
+ * lo_batch_optimize_async on the filtered clouds with the counts, wait.  n_filtered (nullable) receives the counts.
+ * Estimator::preprocess_frame (Estimator.cpp:561-588, VoxelMap.h:73-104) followed by
+ * IterativeClosestPointOptimizer::optimize, per sequence.  Errors as lo_batch_filter_raw. */
+int lo_batch_optimize_raw(lo_batch* b, const float* const* raw, const size_t* n_raw, int stride, float voxel_size,
+                          const float* T_init, lo_batch_rec* out, size_t* n_filtered);
 
 /* ---- single-stage entry points (parity harness; each synchronous) ---- */
 /* ---- device preprocessing + optimize (Estimator::preprocess_frame, Estimator.cpp:561-588) ----

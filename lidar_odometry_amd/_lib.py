@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = (
     "lo_build_normal_equations", "lo_pko_sample_indices", "lo_pko_sample_indices_host", "lo_debug_counters", "lo_debug_counters_ex", "lo_debug_live_bytes", "lo_stage_span", "lo_seq_sum_f64", "lo_seq_sum_f32",
     "lo_batch_create", "lo_batch_destroy", "lo_batch_last_error", "lo_batch_size", "lo_batch_optimize_async",
     "lo_batch_result", "lo_batch_optimize", "lo_batch_bench_correspond",
+    "lo_batch_filter_raw", "lo_batch_filter_raw_host", "lo_batch_filter_ms", "lo_batch_optimize_raw",
     # include/lo_map.h
     "lo_voxelmap_create", "lo_voxelmap_destroy", "lo_voxelmap_update", "lo_voxelmap_l0_count",
     "lo_voxelmap_l1_count", "lo_voxelmap_surfel_count", "lo_voxelmap_get_surfels", "lo_voxelmap_get_l0", "lo_voxelmap_changed_l1", "lo_voxelmap_surfel_at", "lo_voxelmap_surfels_at_keys",
@@ -296,6 +297,13 @@ def lib():
     L.lo_batch_result.argtypes = [vp, C.POINTER(LoBatchRec), dp]
     L.lo_batch_bench_correspond.argtypes = [vp, C.c_int, fp]
     L.lo_batch_optimize.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), fp, C.POINTER(LoBatchRec)]
+    L.lo_batch_filter_raw.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_int, C.c_float,
+                                      C.POINTER(C.c_size_t)]
+    L.lo_batch_filter_raw_host.argtypes = L.lo_batch_filter_raw.argtypes
+    L.lo_batch_filter_ms.restype = C.c_double
+    L.lo_batch_filter_ms.argtypes = [vp]
+    L.lo_batch_optimize_raw.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_int, C.c_float, fp,
+                                        C.POINTER(LoBatchRec), C.POINTER(C.c_size_t)]
     L.lo_voxelmap_create.restype = vp
     L.lo_voxelmap_create.argtypes = [C.c_float, C.c_int, C.c_float, C.c_int]
     L.lo_voxelmap_destroy.argtypes = [vp]

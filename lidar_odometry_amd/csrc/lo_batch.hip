@@ -4,6 +4,11 @@
 // (blockIdx.y = job).  The per-job KParams live in device memory (the batched kernels read them with scalar
 // loads); they are rebuilt on the host every call but uploaded only when a job's scan pointer, size or map
 // table changed.  The initial poses travel in a separate 12-float-per-job array (KParams::T0p).
+//
+// Raw scans enter through lo_batch_filter_raw*: Estimator::preprocess_frame's FastVoxelFilter (Estimator.cpp:561-588,
+// VoxelMap.h:73-104) for every job in one set of five batched launches (lo_vfilter.hip k_vf_*_b), each job on its own
+// context's filter buffers and into its context's d_pts.  The counts come back to the host in one copy: the optimize
+// sizes its grids and sorts the jobs into its three classes from them.
 #include "lo_ctx_def.h"
 
 static constexpr int kBatchPkoWGs = 256;    // PKO workgroups per launch over all jobs (>= 1 per job; measured best)
@@ -48,6 +53,15 @@ struct lo_batch {
     hipEvent_t ev_go = nullptr;      // reference-exact jobs: the batch's uploads done (their streams wait on it)
     std::vector<hipEvent_t> ev_ex;   //   and each exact job's scan finished (the batch stream waits on them)
     int nlock = 0;                   // jobs of the last call that ran in lockstep (the first nlock params)
+    // lo_batch_filter_raw*: the jobs' filter descriptors (rebuilt and uploaded every call), their counts, and the
+    // events around the five filter launches (lo_batch_filter_ms)
+    DevBuf<VfJob> d_jobs;
+    PinnedBuf<VfJob> h_jobs;
+    DevBuf<int> d_cnt;
+    PinnedBuf<int> h_cnt;
+    std::vector<size_t> nf;          // lo_batch_optimize_raw: the counts handed to lo_batch_optimize_async
+    hipEvent_t evf0 = nullptr, evf1 = nullptr;
+    bool filt_timed = false;
     bool pending = false;
 };
 
@@ -64,6 +78,13 @@ static int batch_alloc(lo_batch* b) {
     LO_HIP(b, hipEventCreate(&b->ev0));
     LO_HIP(b, hipEventCreate(&b->ev1));
     LO_HIP(b, hipEventCreateWithFlags(&b->ev_go, hipEventDisableTiming));
+    LO_HIP(b, b->d_jobs.reserve(B));
+    LO_HIP(b, b->h_jobs.reserve(B));
+    LO_HIP(b, b->d_cnt.reserve(B));
+    LO_HIP(b, b->h_cnt.reserve(B));
+    LO_HIP(b, hipEventCreate(&b->evf0));
+    LO_HIP(b, hipEventCreate(&b->evf1));
+    b->nf.assign(B, 0);
     LO_HIP(b, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pko_tb<4, false>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kMaxBlocks * sizeof(int))));
     LO_HIP(b, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pko_tb<1, true>),
@@ -75,6 +96,63 @@ static int batch_alloc(lo_batch* b) {
     LO_HIP(b, exact_scale_c_prepare());
     b->T_in.assign(B * 12, 0.0f);
     b->n.assign(B, 0);
+    return LO_OK;
+}
+
+// The batched filter behind lo_batch_filter_raw (host = false: raw[j] is device-readable as it is) and
+// lo_batch_filter_raw_host (host = true: pinned memory is read in place, pageable memory staged in the context's
+// d_raw on the batch stream).  Every argument is checked before anything is enqueued.
+static int batch_filter(lo_batch* b, const float* const* raw, const size_t* n_raw, int stride, float voxel_size,
+                        size_t* n_out, bool host) {
+    if (!b) return LO_ERR_ARG;
+    if (!raw || !n_raw || !n_out) { b->err = "null argument"; return LO_ERR_ARG; }
+    if (stride < 1 || !(voxel_size > 0.0f)) { b->err = "stride must be >= 1 and voxel_size > 0"; return LO_ERR_ARG; }
+    if (b->pending) { b->err = "batch in flight: call lo_batch_result first"; return LO_ERR_STATE; }
+    const int B = static_cast<int>(b->ctx.size());
+    const size_t st = static_cast<size_t>(stride);
+    for (int j = 0; j < B; ++j) {
+        if (n_raw[j] > 0 && !raw[j]) { b->err = "null raw scan with n_raw > 0"; return LO_ERR_ARG; }
+        if (n_raw[j] / st + (n_raw[j] % st != 0) > static_cast<size_t>(b->ctx[j]->cfg.max_points)) {
+            b->err = "ceil(n_raw / stride) exceeds max_points";
+            return LO_ERR_CAPACITY;
+        }
+    }
+    LO_HIP(b, hipSetDevice(b->device));
+    size_t max_m = 0;
+    for (int j = 0; j < B; ++j) {
+        lo_ctx* c = b->ctx[j];
+        const size_t m = n_raw[j] / st + (n_raw[j] % st != 0);
+        const float* src = n_raw[j] > 0 ? raw[j] : nullptr;
+        if (host && src) {
+            src = pinned_alias(raw[j]);
+            if (!src) {
+                LO_HIP(b, c->d_raw.reserve(n_raw[j] * 3));
+                LO_HIP(b, hipMemcpyAsync(c->d_raw, raw[j], n_raw[j] * 3 * sizeof(float), hipMemcpyHostToDevice, b->stream));
+                src = c->d_raw;
+            }
+        }
+        // growth frees the old buffers: vf_reserve drains the stream it is given (the batch's), and launches on the
+        // context's own stream may still read them too; the new table's k_vf_init runs on the batch stream, before
+        // the batched insert
+        if (c->vf.ctr != nullptr && m > c->vf.cap) LO_HIP(b, hipStreamSynchronize(c->stream));
+        LO_HIP(b, vf_reserve(c->vf, m, b->stream));
+        b->h_jobs[j] = vf_job(c->vf, src, m, c->d_pts);
+        max_m = std::max(max_m, m);
+    }
+    LO_HIP(b, hipMemcpyAsync(b->d_jobs, b->h_jobs, sizeof(VfJob) * B, hipMemcpyHostToDevice, b->stream));
+    LO_HIP(b, hipEventRecord(b->evf0, b->stream));
+    LO_HIP(b, vf_enqueue_batch(b->d_jobs, B, max_m, stride, voxel_size, b->d_cnt, b->stream));
+    LO_HIP(b, hipEventRecord(b->evf1, b->stream));
+    b->filt_timed = true;
+    LO_HIP(b, hipMemcpyAsync(b->h_cnt, b->d_cnt, sizeof(int) * B, hipMemcpyDeviceToHost, b->stream));
+    LO_HIP(b, hipStreamSynchronize(b->stream));
+    for (int j = 0; j < B; ++j) {
+        lo_ctx* c = b->ctx[j];
+        n_out[j] = static_cast<size_t>(b->h_cnt[j]);
+        c->last_dev_count = true;                      // as after lo_voxel_filter_gpu: lo_filtered_points,
+        *c->h_nf = b->h_cnt[j];                        //   ctx_filtered_device see this scan; its count is known here
+        c->nf_valid = true;
+    }
     return LO_OK;
 }
 
@@ -122,6 +200,8 @@ void lo_batch_destroy(lo_batch* b) {
     if (b->ev0) (void)hipEventDestroy(b->ev0);
     if (b->ev1) (void)hipEventDestroy(b->ev1);
     if (b->ev_go) (void)hipEventDestroy(b->ev_go);
+    if (b->evf0) (void)hipEventDestroy(b->evf0);
+    if (b->evf1) (void)hipEventDestroy(b->evf1);
     for (hipEvent_t e : b->ev_ex) (void)hipEventDestroy(e);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
@@ -327,6 +407,34 @@ int lo_batch_optimize(lo_batch* b, const float* const* pts, const size_t* n, con
         LO_HIP(b, hipMemcpyAsync(b->ctx[j]->d_pts, pts[j], n[j] * 3 * sizeof(float), hipMemcpyHostToDevice, b->stream));
     }
     const int rc = lo_batch_optimize_async(b, nullptr, n, T_init);
+    if (rc != LO_OK) return rc;
+    return lo_batch_result(b, out, nullptr);
+}
+
+int lo_batch_filter_raw(lo_batch* b, const float* const* d_raw, const size_t* n_raw, int stride, float voxel_size,
+                        size_t* n_out) {
+    return batch_filter(b, d_raw, n_raw, stride, voxel_size, n_out, false);
+}
+
+int lo_batch_filter_raw_host(lo_batch* b, const float* const* raw, const size_t* n_raw, int stride, float voxel_size,
+                             size_t* n_out) {
+    return batch_filter(b, raw, n_raw, stride, voxel_size, n_out, true);
+}
+
+double lo_batch_filter_ms(const lo_batch* b) {
+    float ms = -1.0f;
+    if (!b || !b->filt_timed || hipEventElapsedTime(&ms, b->evf0, b->evf1) != hipSuccess) return -1.0;
+    return ms;
+}
+
+int lo_batch_optimize_raw(lo_batch* b, const float* const* raw, const size_t* n_raw, int stride, float voxel_size,
+                          const float* T_init, lo_batch_rec* out, size_t* n_filtered) {
+    if (!b) return LO_ERR_ARG;
+    if (!T_init || !out) { b->err = "null argument"; return LO_ERR_ARG; }
+    int rc = batch_filter(b, raw, n_raw, stride, voxel_size, b->nf.data(), true);
+    if (rc != LO_OK) return rc;
+    if (n_filtered) std::copy(b->nf.begin(), b->nf.end(), n_filtered);
+    rc = lo_batch_optimize_async(b, nullptr, b->nf.data(), T_init);   // NULL d_pts: each context's filtered cloud
     if (rc != LO_OK) return rc;
     return lo_batch_result(b, out, nullptr);
 }

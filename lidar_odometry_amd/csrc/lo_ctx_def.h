@@ -241,6 +241,16 @@ inline int ensure_acc_part(lo_ctx* c) {
     return LO_OK;
 }
 
+// A host scan in pinned memory (lo_host_alloc, hipHostMalloc, hipHostRegister): the device address that aliases it,
+// so the filter reads the sampled points over the bus directly instead of a staging copy of the whole scan.
+inline const float* pinned_alias(const float* p) {
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return nullptr; }   // pageable
+    if (a.type != hipMemoryTypeHost || !a.devicePointer || !a.hostPointer) return nullptr;
+    return reinterpret_cast<const float*>(static_cast<const char*>(a.devicePointer) +
+                                          (reinterpret_cast<const char*>(p) - static_cast<const char*>(a.hostPointer)));
+}
+
 inline void set_kd_params(lo_ctx* c, KParams& P, const PointGrid& G) {
     P.tab = c->d_kd_plane;
     P.kd_pts = G.d_pts;

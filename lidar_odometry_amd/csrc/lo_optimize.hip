@@ -647,16 +647,6 @@ int lo_icp_optimize_raw_async(lo_ctx* c, const float* d_raw, size_t n_raw, int s
     return enqueue_optimize(c, c->d_pts, static_cast<size_t>(m), T_init, c->vf.n_out);
 }
 
-// A host scan in pinned memory (lo_host_alloc, hipHostMalloc, hipHostRegister): the device address that aliases it,
-// so the filter reads the sampled points over the bus directly instead of a staging copy of the whole scan.
-static const float* pinned_alias(const float* p) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return nullptr; }   // pageable
-    if (a.type != hipMemoryTypeHost || !a.devicePointer || !a.hostPointer) return nullptr;
-    return reinterpret_cast<const float*>(static_cast<const char*>(a.devicePointer) +
-                                          (reinterpret_cast<const char*>(p) - static_cast<const char*>(a.hostPointer)));
-}
-
 void* lo_host_alloc(size_t bytes) {
     void* p = nullptr;
     if (hipHostMalloc(&p, std::max<size_t>(bytes, 1), hipHostMallocDefault) != hipSuccess) return nullptr;

@@ -38,10 +38,37 @@ struct VfBuffers {
     int* n_out = nullptr;        // &ctr->n_out
 };
 
+// One job of the batched filter (k_vf_*_b): what the single-scan launches take as arguments, in device memory.
+struct VfJob {
+    const float* raw;            // device memory or the device alias of pinned host memory (null when m = 0)
+    int m;                       // samples = ceil(n_raw / stride)
+    int l2;                      // log2 of the table size
+    uint64_t mask;               // table size - 1
+    uint64_t* tkey;
+    VfSlot* tslot;
+    int32_t* sslot;
+    float* samp;
+    int2* loc;
+    int2* blk;
+    int2* blk_pre;
+    int32_t* bucket;
+    int32_t* mid;
+    int32_t* big;
+    VfCounters* ctr;
+    float* out;                  // the job's filtered cloud (its context's d_pts)
+};
+
 hipError_t vf_reserve(VfBuffers& b, size_t m, hipStream_t s);
 // Filter d_raw (n_raw AoS float3) into d_out on stream s; the output count lands in b.n_out (device).
 // m_out = ceil(n_raw / stride), an upper bound of the output count.
 hipError_t vf_enqueue(VfBuffers& b, const float* d_raw, size_t n_raw, int stride, float voxel_size, float* d_out,
                       hipStream_t s, int& m_out);
+
+// The descriptor of a job of m samples on buffers b (reserved for at least m samples), output into d_out.
+VfJob vf_job(const VfBuffers& b, const float* d_raw, size_t m, float* d_out);
+// Enqueue the filter of B jobs (d_jobs: their descriptors in device memory; max_m: the largest job's samples) on
+// stream s: five batched launches.  Job j's count lands in its counters' n_out and in d_counts[j].
+hipError_t vf_enqueue_batch(const VfJob* d_jobs, int B, size_t max_m, int stride, float voxel_size, int* d_counts,
+                            hipStream_t s);
 
 }  // namespace lo

@@ -64,10 +64,10 @@ __global__ __launch_bounds__(256) void k_vf_init(uint64_t* tkey, VfSlot* tslot, 
 
 // raw may be device memory or pinned host memory (read over the bus exactly once, here: later kernels read the
 // compact per-sample copy)
-__global__ __launch_bounds__(256) void k_vf_insert(const float* __restrict__ raw, int stride, float inv, int m,
-                                                   uint64_t* tkey, VfSlot* tslot, uint64_t mask, int l2,
-                                                   int32_t* __restrict__ sslot, float* __restrict__ samp) {
-    const int j = blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void vf_insert_body(int bx, const float* __restrict__ raw, int stride, float inv, int m,
+                                               uint64_t* tkey, VfSlot* tslot, uint64_t mask, int l2,
+                                               int32_t* __restrict__ sslot, float* __restrict__ samp) {
+    const int j = bx * 256 + threadIdx.x;
     if (j >= m) return;
     const float* p = vf_point(raw, stride, j);
     const float x = p[0], y = p[1], z = p[2];
@@ -89,6 +89,23 @@ __global__ __launch_bounds__(256) void k_vf_insert(const float* __restrict__ raw
     atomicMax(&tslot[b].last, static_cast<uint32_t>(j));
     atomicAdd(&tslot[b].cnt, 1u);
     sslot[j] = static_cast<int32_t>(b);
+}
+
+__global__ __launch_bounds__(256) void k_vf_insert(const float* __restrict__ raw, int stride, float inv, int m,
+                                                   uint64_t* tkey, VfSlot* tslot, uint64_t mask, int l2,
+                                                   int32_t* __restrict__ sslot, float* __restrict__ samp) {
+    vf_insert_body(blockIdx.x, raw, stride, inv, m, tkey, tslot, mask, l2, sslot, samp);
+}
+
+// The batched forms (k_vf_*_b, lo_batch_filter_raw): blockIdx.y = job, the job's arguments from its descriptor (read
+// with scalar loads), the grid sized for the largest job.  A block beyond its job's samples leaves before it touches
+// the job's memory and before any barrier (the test is block-uniform).  Each job runs the single-scan body on its own
+// context's buffers, so its output is the single-scan kernels' bit for bit and its table ends empty the same way.
+__global__ __launch_bounds__(256) void k_vf_insert_b(const VfJob* __restrict__ jobs, int stride, float inv) {
+    const VfJob* J = jobs + blockIdx.y;
+    const int m = J->m;
+    if (static_cast<int>(blockIdx.x) * 256 >= m) return;
+    vf_insert_body(blockIdx.x, J->raw, stride, inv, m, J->tkey, J->tslot, J->mask, J->l2, J->sslot, J->samp);
 }
 
 // inclusive scan of an int2 over the 64 lanes of a wave
@@ -127,12 +144,11 @@ __device__ __forceinline__ int2 block_excl_scan2(int2 v, int2& tot, int2* s_w /*
 // Every block writes its (heads, members) totals; the exclusive prefix over the blocks is formed by each consumer
 // workgroup itself (vf_block_prefix) -- r05's last-block-done hand-off needed agent-scope fences (an L2 write-back per
 // block) and cost ~14 us at KITTI size.
-__global__ __launch_bounds__(kVfHeadsBlock) void k_vf_heads(int m, const int32_t* __restrict__ sslot,
-                                                            const VfSlot* __restrict__ tslot, int2* __restrict__ loc,
-                                                            int2* blk) {
+__device__ __forceinline__ void vf_heads_body(int bx, int m, const int32_t* __restrict__ sslot,
+                                              const VfSlot* __restrict__ tslot, int2* __restrict__ loc, int2* blk) {
     __shared__ int2 s_w[kVfHeadsBlock / 64 + 1];
     const int tid = threadIdx.x;
-    const int j = blockIdx.x * kVfHeadsBlock + tid;
+    const int j = bx * kVfHeadsBlock + tid;
     int2 v = make_int2(0, 0);
     if (j < m) {
         const int b = sslot[j];
@@ -144,7 +160,20 @@ __global__ __launch_bounds__(kVfHeadsBlock) void k_vf_heads(int m, const int32_t
     int2 tot;
     const int2 ex = block_excl_scan2<kVfHeadsBlock>(v, tot, s_w);
     if (v.x) loc[j] = ex;
-    if (tid == 0) blk[blockIdx.x] = tot;
+    if (tid == 0) blk[bx] = tot;
+}
+
+__global__ __launch_bounds__(kVfHeadsBlock) void k_vf_heads(int m, const int32_t* __restrict__ sslot,
+                                                            const VfSlot* __restrict__ tslot, int2* __restrict__ loc,
+                                                            int2* blk) {
+    vf_heads_body(blockIdx.x, m, sslot, tslot, loc, blk);
+}
+
+__global__ __launch_bounds__(kVfHeadsBlock) void k_vf_heads_b(const VfJob* __restrict__ jobs) {
+    const VfJob* J = jobs + blockIdx.y;
+    const int m = J->m;
+    if (static_cast<int>(blockIdx.x) * kVfHeadsBlock >= m) return;
+    vf_heads_body(blockIdx.x, m, J->sslot, J->tslot, J->loc, J->blk);
 }
 
 // The exclusive prefix of the heads blocks' totals into out[0 .. nb] (out[nb] = the grand total; LDS or global), by
@@ -172,30 +201,34 @@ __device__ __forceinline__ int2 vf_head_offsets(const int2* loc, const int2* blk
 // sample sums the totals before its head's block), block 0 also publishes it (blk_pre, nb + 1 entries) and the pass's
 // counters for the later launches
 constexpr int kVfMaxPre = 1024;
-__global__ __launch_bounds__(256) void k_vf_place(int m, const int32_t* __restrict__ sslot, VfSlot* tslot,
-                                                  const int2* __restrict__ loc, const int2* __restrict__ blk,
-                                                  int2* __restrict__ blk_pre, VfCounters* ctr,
-                                                  int32_t* __restrict__ bucket) {
+__device__ __forceinline__ void vf_place_body(int bx, int m, const int32_t* __restrict__ sslot, VfSlot* tslot,
+                                              const int2* __restrict__ loc, const int2* __restrict__ blk,
+                                              int2* __restrict__ blk_pre, VfCounters* ctr,
+                                              int32_t* __restrict__ bucket, int* __restrict__ count_out) {
     __shared__ int2 s_pre[kVfMaxPre + 1];
     const int nb = (m + kVfHeadsBlock - 1) / kVfHeadsBlock;
-    const int j = blockIdx.x * 256 + threadIdx.x;
+    const int j = bx * 256 + threadIdx.x;
     int b = -1, h = 0;
     if (j < m) {                                     // the sample's loads go out before the prefix is formed
         b = sslot[j];
         if (b >= 0) h = static_cast<int>(tslot[b].first);
     }
-    if (blockIdx.x == 0) {
+    if (bx == 0) {
         vf_block_prefix(blk, nb, blk_pre);
         if (threadIdx.x == 0) { ctr->n_mid = 0; ctr->n_big = 0; }
     }
     if (nb <= kVfMaxPre) {
         vf_block_prefix(blk, nb, s_pre);
         __syncthreads();
-        if (blockIdx.x == 0 && threadIdx.x == 0) ctr->n_out = s_pre[nb].x;
-    } else if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (bx == 0 && threadIdx.x == 0) {
+            ctr->n_out = s_pre[nb].x;
+            if (count_out) *count_out = s_pre[nb].x;
+        }
+    } else if (bx == 0 && threadIdx.x == 0) {
         int tot = 0;
         for (int q = 0; q < nb; ++q) tot += blk[q].x;
         ctr->n_out = tot;
+        if (count_out) *count_out = tot;
     }
     if (j >= m || b < 0) return;
     int start;
@@ -208,6 +241,22 @@ __global__ __launch_bounds__(256) void k_vf_place(int m, const int32_t* __restri
     }
     const unsigned r = atomicAdd(&tslot[b].fill, 1u);
     bucket[start + static_cast<int>(r)] = j;
+}
+
+__global__ __launch_bounds__(256) void k_vf_place(int m, const int32_t* __restrict__ sslot, VfSlot* tslot,
+                                                  const int2* __restrict__ loc, const int2* __restrict__ blk,
+                                                  int2* __restrict__ blk_pre, VfCounters* ctr,
+                                                  int32_t* __restrict__ bucket) {
+    vf_place_body(blockIdx.x, m, sslot, tslot, loc, blk, blk_pre, ctr, bucket, nullptr);
+}
+
+// block 0 of every job runs even for an empty job (m = 0: no heads block ran, the prefix of zero totals is 0): it
+// publishes the job's count, in its context's counters and in the batch's contiguous counts[job]
+__global__ __launch_bounds__(256) void k_vf_place_b(const VfJob* __restrict__ jobs, int* __restrict__ counts) {
+    const VfJob* J = jobs + blockIdx.y;
+    const int m = J->m;
+    if (blockIdx.x > 0 && static_cast<int>(blockIdx.x) * 256 >= m) return;
+    vf_place_body(blockIdx.x, m, J->sslot, J->tslot, J->loc, J->blk, J->blk_pre, J->ctr, J->bucket, counts + blockIdx.y);
 }
 
 // ascending bitonic sort of N register values (compile-time indices: stays in VGPRs)
@@ -229,12 +278,12 @@ __device__ __forceinline__ void bitonic_regs(int (&a)[N]) {
             }
 }
 
-__global__ __launch_bounds__(256) void k_vf_small(const float* __restrict__ samp, int m,
-                                                  const int32_t* __restrict__ sslot, uint64_t* tkey, VfSlot* tslot,
-                                                  const int2* __restrict__ loc, const int2* __restrict__ blk,
-                                                  const int32_t* __restrict__ bucket, int32_t* mid, int32_t* big,
-                                                  VfCounters* ctr, float* __restrict__ out) {
-    const int j = blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void vf_small_body(int bx, const float* __restrict__ samp, int m,
+                                              const int32_t* __restrict__ sslot, uint64_t* tkey, VfSlot* tslot,
+                                              const int2* __restrict__ loc, const int2* __restrict__ blk,
+                                              const int32_t* __restrict__ bucket, int32_t* mid, int32_t* big,
+                                              VfCounters* ctr, float* __restrict__ out) {
+    const int j = bx * 256 + threadIdx.x;
     if (j >= m) return;
     const int b = sslot[j];
     if (b < 0) return;
@@ -270,16 +319,34 @@ __global__ __launch_bounds__(256) void k_vf_small(const float* __restrict__ samp
     vf_reset(tkey, tslot, b);
 }
 
-__global__ __launch_bounds__(256) void k_vf_wide(const float* __restrict__ samp,
-                                                 const int32_t* __restrict__ sslot, uint64_t* tkey, VfSlot* tslot,
-                                                 const int2* __restrict__ loc, const int2* __restrict__ blk,
-                                                 const int32_t* __restrict__ bucket, const int32_t* __restrict__ mid,
-                                                 const int32_t* __restrict__ big, const VfCounters* ctr,
-                                                 float* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_vf_small(const float* __restrict__ samp, int m,
+                                                  const int32_t* __restrict__ sslot, uint64_t* tkey, VfSlot* tslot,
+                                                  const int2* __restrict__ loc, const int2* __restrict__ blk,
+                                                  const int32_t* __restrict__ bucket, int32_t* mid, int32_t* big,
+                                                  VfCounters* ctr, float* __restrict__ out) {
+    vf_small_body(blockIdx.x, samp, m, sslot, tkey, tslot, loc, blk, bucket, mid, big, ctr, out);
+}
+
+__global__ __launch_bounds__(256) void k_vf_small_b(const VfJob* __restrict__ jobs) {
+    const VfJob* J = jobs + blockIdx.y;
+    const int m = J->m;
+    if (static_cast<int>(blockIdx.x) * 256 >= m) return;
+    vf_small_body(blockIdx.x, J->samp, m, J->sslot, J->tkey, J->tslot, J->loc, J->blk_pre, J->bucket, J->mid, J->big,
+                  J->ctr, J->out);
+}
+
+// bx / gx: this workgroup's index and the workgroup count of its job (the voxels are dealt round robin; every
+// voxel's sums are taken in sample-index order whatever gx is)
+__device__ __forceinline__ void vf_wide_body(int bx, int gx, const float* __restrict__ samp,
+                                             const int32_t* __restrict__ sslot, uint64_t* tkey, VfSlot* tslot,
+                                             const int2* __restrict__ loc, const int2* __restrict__ blk,
+                                             const int32_t* __restrict__ bucket, const int32_t* __restrict__ mid,
+                                             const int32_t* __restrict__ big, const VfCounters* ctr,
+                                             float* __restrict__ out) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     // ---- 17..64 members: one wave per voxel ----
     const int n_mid = ctr->n_mid;
-    for (int q = blockIdx.x * 4 + wid; q < n_mid; q += gridDim.x * 4) {
+    for (int q = bx * 4 + wid; q < n_mid; q += gx * 4) {
         const int j = mid[q];
         const int b = sslot[j];
         const int c = static_cast<int>(tslot[b].cnt);
@@ -315,7 +382,7 @@ __global__ __launch_bounds__(256) void k_vf_wide(const float* __restrict__ samp,
     __shared__ int s_wc[4];
     __shared__ int s_srt[kVfBigSort];
     const int n_big = ctr->n_big;
-    for (int q = blockIdx.x; q < n_big; q += gridDim.x) {
+    for (int q = bx; q < n_big; q += gx) {
         const int j = big[q];
         const int b = sslot[j];
         const VfSlot s = tslot[b];
@@ -395,6 +462,23 @@ __global__ __launch_bounds__(256) void k_vf_wide(const float* __restrict__ samp,
     }
 }
 
+__global__ __launch_bounds__(256) void k_vf_wide(const float* __restrict__ samp,
+                                                 const int32_t* __restrict__ sslot, uint64_t* tkey, VfSlot* tslot,
+                                                 const int2* __restrict__ loc, const int2* __restrict__ blk,
+                                                 const int32_t* __restrict__ bucket, const int32_t* __restrict__ mid,
+                                                 const int32_t* __restrict__ big, const VfCounters* ctr,
+                                                 float* __restrict__ out) {
+    vf_wide_body(blockIdx.x, gridDim.x, samp, sslot, tkey, tslot, loc, blk, bucket, mid, big, ctr, out);
+}
+
+// gridDim.x workgroups per job (fewer than the single kernel's kVfWideGrid when the batch is large: vf_wide_groups)
+__global__ __launch_bounds__(256) void k_vf_wide_b(const VfJob* __restrict__ jobs) {
+    const VfJob* J = jobs + blockIdx.y;
+    if (J->m == 0) return;
+    vf_wide_body(blockIdx.x, gridDim.x, J->samp, J->sslot, J->tkey, J->tslot, J->loc, J->blk_pre, J->bucket, J->mid,
+                 J->big, J->ctr, J->out);
+}
+
 // ---------------------------------------------------------------- host side (called from lo_optimize.hip)
 // Grows the filter's buffers on the context stream s: the old buffers may still be read by filter launches
 // queued on s, so s (only) is drained before they are freed, and the table init runs on s, ordered before the
@@ -455,6 +539,51 @@ hipError_t vf_enqueue(VfBuffers& b, const float* d_raw, size_t n_raw, int stride
                        b.bucket, b.mid, b.big, b.ctr, d_out);
     hipLaunchKernelGGL(k_vf_wide, dim3(kVfWideGrid), t256, 0, s, b.samp, b.sslot, b.tkey, b.tslot, b.loc,
                        b.blk_pre, b.bucket, b.mid, b.big, b.ctr, d_out);
+    return hipGetLastError();
+}
+
+VfJob vf_job(const VfBuffers& b, const float* d_raw, size_t m, float* d_out) {
+    int l2 = 0;
+    while ((size_t(1) << l2) < b.tcap) ++l2;
+    VfJob J{};
+    J.raw = d_raw;
+    J.m = static_cast<int>(m);
+    J.l2 = l2;
+    J.mask = static_cast<uint64_t>(b.tcap - 1);
+    J.tkey = b.tkey;
+    J.tslot = b.tslot;
+    J.sslot = b.sslot;
+    J.samp = b.samp;
+    J.loc = b.loc;
+    J.blk = b.blk;
+    J.blk_pre = b.blk_pre;
+    J.bucket = b.bucket;
+    J.mid = b.mid;
+    J.big = b.big;
+    J.ctr = b.ctr;
+    J.out = d_out;
+    return J;
+}
+
+// k_vf_wide_b's workgroups per job.  The single kernel's 64 are sized for one scan alone on the chip; in a batch the
+// jobs fill it, so a job gets one workgroup per 2048 samples (a KITTI scan's 15k samples: 8), more while the batch is
+// small (1024 workgroups over all jobs), 64 at the most.  The output does not depend on it.
+static int vf_wide_groups(int B, size_t max_m) {
+    const size_t per_job = std::max<size_t>((max_m + 2047) / 2048, static_cast<size_t>(1024 / B));
+    return static_cast<int>(std::min<size_t>(std::max<size_t>(per_job, 1), kVfWideGrid));
+}
+
+hipError_t vf_enqueue_batch(const VfJob* d_jobs, int B, size_t max_m, int stride, float voxel_size, int* d_counts,
+                            hipStream_t s) {
+    const float inv = 1.0f / voxel_size;                 // m_inv_voxel_size (VoxelMap.h:57)
+    const unsigned nb = static_cast<unsigned>(B);
+    const dim3 g256(static_cast<unsigned>(std::max<size_t>((max_m + 255) / 256, 1)), nb), t256(256);
+    const dim3 gh(static_cast<unsigned>(std::max<size_t>((max_m + kVfHeadsBlock - 1) / kVfHeadsBlock, 1)), nb);
+    hipLaunchKernelGGL(k_vf_insert_b, g256, t256, 0, s, d_jobs, stride, inv);
+    hipLaunchKernelGGL(k_vf_heads_b, gh, dim3(kVfHeadsBlock), 0, s, d_jobs);
+    hipLaunchKernelGGL(k_vf_place_b, g256, t256, 0, s, d_jobs, d_counts);
+    hipLaunchKernelGGL(k_vf_small_b, g256, t256, 0, s, d_jobs);
+    hipLaunchKernelGGL(k_vf_wide_b, dim3(static_cast<unsigned>(vf_wide_groups(B, max_m)), nb), t256, 0, s, d_jobs);
     return hipGetLastError();
 }
 

@@ -425,6 +425,8 @@ class BatchOptimizer:
         if not self._b:
             raise RuntimeError(f"lo_batch_create failed (code {err.value})")
         self.last_gpu_ms = 0.0
+        self.last_filter_ms = -1.0
+        self.last_counts = []
 
     def close(self):
         h = getattr(self, "_b", None)
@@ -470,6 +472,47 @@ class BatchOptimizer:
         ns = (C.c_size_t * B)(*[len(p) for p in pts])
         recs = (LoBatchRec * B)()
         self._check(lib().lo_batch_optimize(self._b, ptrs, ns, _fptr(T), recs))
+        return self._results(recs)
+
+    def _raw_args(self, raws):
+        B = len(self.optimizers)
+        pts = [_as_pts(p) for p in raws]            # a pinned_empty array passes through as it is (read in place)
+        if len(pts) != B:
+            raise ValueError(f"need {B} raw scans")
+        ptrs = (C.c_void_p * B)(*[p.ctypes.data if len(p) else None for p in pts])
+        ns = (C.c_size_t * B)(*[len(p) for p in pts])
+        return pts, ptrs, ns
+
+    def filter_raw(self, raws, stride: int = 8, voxel_size: float = 0.5):
+        """Estimator::preprocess_frame's FastVoxelFilter for every job in one set of batched launches
+        (lo_batch_filter_raw_host): host raw scans in (pinned ones are read in place), the filtered counts out.
+        Afterwards ``optimizers[j].filtered_points()`` is job j's feature cloud, and
+        ``optimize_async([0] * B, counts, T)`` optimizes the filtered clouds."""
+        B = len(self.optimizers)
+        pts, ptrs, ns = self._raw_args(raws)
+        counts = (C.c_size_t * B)()
+        self._check(lib().lo_batch_filter_raw_host(self._b, ptrs, ns, int(stride), float(voxel_size), counts))
+        del pts
+        self.last_filter_ms = float(lib().lo_batch_filter_ms(self._b))
+        return [int(n) for n in counts]
+
+    def optimize_raw(self, voxel_maps, raws, initial_transforms, stride: int = 8, voxel_size: float = 0.5):
+        """Host raw scans in, one BatchResult per job out (lo_batch_optimize_raw): the batched filter, then the batched
+        optimize on the filtered clouds.  ``last_counts`` holds the filtered counts."""
+        B = len(self.optimizers)
+        if voxel_maps is not None:
+            for o, vm in zip(self.optimizers, voxel_maps):
+                o._sync_map(vm)
+        pts, ptrs, ns = self._raw_args(raws)
+        T = np.ascontiguousarray(np.stack([_as_pose(t) for t in initial_transforms]), dtype=np.float32)
+        if T.shape != (B, 12):
+            raise ValueError(f"need {B} initial transforms")
+        recs = (LoBatchRec * B)()
+        counts = (C.c_size_t * B)()
+        self._check(lib().lo_batch_optimize_raw(self._b, ptrs, ns, int(stride), float(voxel_size), _fptr(T), recs, counts))
+        del pts
+        self.last_filter_ms = float(lib().lo_batch_filter_ms(self._b))
+        self.last_counts = [int(n) for n in counts]
         return self._results(recs)
 
     def optimize_async(self, device_ptrs, counts, initial_transforms):
