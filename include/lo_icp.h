@@ -237,7 +237,15 @@ int lo_bench_correspond_rr(lo_ctx* const* ctxs, const float* const* d_pts, const
  * (blockIdx.y = job).  Each job computes exactly what lo_icp_optimize computes on its context (bit-identical:
  * same kernels, same per-job reductions).  The reference has no batch entry point; this is the multi-sequence
  * form of IterativeClosestPointOptimizer::optimize (IterativeClosestPointOptimizer.cpp:255-463) called once
- * per sequence.  Requirements: surfel correspondence mode, one device, equal max_iterations.  A context in
+ * per sequence.  Requirements: one correspondence mode per batch (the contexts are all in surfel mode or all in
+ * KDTree mode, use_surfel_correspondence = 0; a mixed set is refused with LO_ERR_ARG), one device, equal
+ * max_iterations.  A KDTree batch searches every job's five neighbours, answers its unresolved queries and fits its
+ * planes in one launch each per iteration (k_knn_b, k_knn_brute_b, k_plane_b); a job whose grid is the all-pairs
+ * form runs on its own context stream inside the batch call.  Distance ties: a job on a host-built grid
+ * (lo_map_set_points) ranks them on the device in the kd visit order; a job on a device-built grid
+ * (lo_devmap_sync_points, no visit order) that meets a deciding tie is run again through its context by
+ * lo_batch_result, with the order built on the host, exactly as lo_icp_result does -- the record is that run's, and
+ * the context's lo_kd_reruns counts it.  A context in
  * reference-exact mode (lo_set_exact) runs its own exact GN loop on its context stream inside the batch call (the
  * sequential-sum reproductions have no lockstep form), ordered after the batch's uploads and before its record
  * export, bit-identical to its lo_icp_optimize.  The batch runs on its own stream; the contexts must be idle while
@@ -250,7 +258,7 @@ typedef struct lo_batch_rec {
     int    n_corr;         /* last iteration */
     float  initial_cost;
     float  final_cost;
-    float  pad;
+    float  pad;            /* 0 */
     double alpha;          /* last PKO Huber delta */
 } lo_batch_rec;
 lo_batch*   lo_batch_create(lo_ctx* const* ctxs, int count, int* err);
@@ -264,7 +272,8 @@ int lo_batch_optimize_async(lo_batch* b, const float* const* d_pts, const size_t
 /* Waits for the batch; out[count] receives one record per job.  Returns LO_OK or a negative error. */
 int lo_batch_result(lo_batch* b, lo_batch_rec* out, double* gpu_ms);
 /* Timing harness: reps back-to-back launches of the batched correspondence kernel over the last batch's jobs at
- * their initial poses (after one resetting launch); writes the average device time per launch (HIP events).
+ * their initial poses (after one resetting launch); writes the average device time per launch (HIP events).  For a
+ * KDTree batch a "launch" is the whole correspondence stage: the search, the unresolved pass and the plane fit.
  * Leaves every job's GN state at its initial pose. */
 int lo_batch_bench_correspond(lo_batch* b, int reps, float* avg_ms);
 /* Host points in, records out (H2D of every scan on the batch stream, enqueue, wait). */

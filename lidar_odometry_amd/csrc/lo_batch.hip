@@ -9,7 +9,14 @@
 // VoxelMap.h:73-104) for every job in one set of five batched launches (lo_vfilter.hip k_vf_*_b), each job on its own
 // context's filter buffers and into its context's d_pts.  The counts come back to the host in one copy: the optimize
 // sizes its grids and sorts the jobs into its three classes from them.
+//
+// One batch has one correspondence mode.  A KDTree batch (every context use_surfel_correspondence = 0) replaces the
+// k_correspond_b launch of each iteration by k_knn_b, k_knn_brute_b and k_plane_b (lo_kdtree.hip): the per-point
+// planes, residuals, ballots and block statistics they write are what the surfel launch writes, so everything after
+// them is the same launch sequence.
 #include "lo_ctx_def.h"
+
+#include <climits>
 
 static constexpr int kBatchPkoWGs = 256;    // PKO workgroups per launch over all jobs (>= 1 per job; measured best)
 // one single-wave PKO workgroup per job (k_pko_tb<1, true>) is opt-in (LO_BATCH_ONE_WAVE=1): with the JS phase's
@@ -20,9 +27,14 @@ static constexpr int kBatchOneWaveMin = 0x7fffffff;
 // the fused form's fp64 solve holds the 8-wave accumulate at 128 VGPRs (2 workgroups per CU; split: 70, 3 per CU).
 // Measured: 4096 jobs 1.037M -> 1.090M scans/s, 1024 857k -> 875k; at 64-256 jobs the extra launch costs ~1 %.
 static constexpr int kBatchSplitSolveMin = 1024;
+// KDTree batches, the unresolved pass (k_knn_brute_b): at most this many 1024-thread workgroups over all jobs (two per
+// CU), and at most kBatchBrutePerJob of them on one job (what a single context's k_knn_brute launch gets)
+static constexpr int kBatchBruteWGs = 512;
+static constexpr int kBatchBrutePerJob = 64;
 
 struct lo_batch {
     std::vector<lo_ctx*> ctx;
+    bool kd = false;                 // KDTree-mode contexts (all of them: one batch has one correspondence mode)
     int device = 0;
     int max_iters = 0;
     int pko_max = 1;                 // min over contexts of the single-scan PKO grid
@@ -42,13 +54,20 @@ struct lo_batch {
     std::vector<size_t> n;
     struct Sig {
         const lo_ctx* ctx; uint64_t gen; const float* pts; int n; const Slot* tab; uint32_t log2cap; int exact;
+        // KDTree jobs: the grid in place of the surfel table (tab is then the context's own plane buffer) -- its point
+        // and cell arrays, point count, whether it carries the kd visit order, and its geometry (zero for surfel jobs)
+        const float4* kd_pts; const uint32_t* kd_start; int kd_m; bool kd_order; int kd_org[3], kd_dim[3]; float kd_h;
         // field by field: the padding after n is not initialised, so a byte compare could report a change every call
         bool operator==(const Sig& o) const {
-            return ctx == o.ctx && gen == o.gen && pts == o.pts && n == o.n && tab == o.tab && log2cap == o.log2cap &&
-                   exact == o.exact;
+            bool same = ctx == o.ctx && gen == o.gen && pts == o.pts && n == o.n && tab == o.tab &&
+                        log2cap == o.log2cap && exact == o.exact && kd_pts == o.kd_pts && kd_start == o.kd_start &&
+                        kd_m == o.kd_m && kd_order == o.kd_order && kd_h == o.kd_h;
+            for (int a = 0; a < 3; ++a) same = same && kd_org[a] == o.kd_org[a] && kd_dim[a] == o.kd_dim[a];
+            return same;
         }
     };
     std::vector<Sig> sig;            // what d_P currently holds, per active slot
+    std::vector<const float*> act_pts;   // the active jobs' scans (a KDTree job's re-run after a distance tie)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t ev_go = nullptr;      // reference-exact jobs: the batch's uploads done (their streams wait on it)
     std::vector<hipEvent_t> ev_ex;   //   and each exact job's scan finished (the batch stream waits on them)
@@ -94,6 +113,9 @@ static int batch_alloc(lo_batch* b) {
     // reference-exact jobs' iteration-0 scale (k_exact_scale_cb, up to 80 KB of dynamic LDS): a process that only
     // batches must not depend on a single-context exact optimize having set the attribute first
     LO_HIP(b, exact_scale_c_prepare());
+    // KDTree batches: k_knn_b, k_knn_brute_b and k_plane_b use static LDS only (no attribute to set); a job that runs
+    // on its own context (a large exact job, an all-pairs grid, a re-run after a tie) goes through enqueue_optimize,
+    // whose kernels' attributes lo_create set for a KDTree context (kd_alloc)
     b->T_in.assign(B * 12, 0.0f);
     b->n.assign(B, 0);
     return LO_OK;
@@ -156,6 +178,23 @@ static int batch_filter(lo_batch* b, const float* const* raw, const size_t* n_ra
     return LO_OK;
 }
 
+// The correspondence stage of one lockstep iteration for the first nact jobs of d_P: the surfel lookup, or (KDTree
+// batch) the grid search, the unresolved queries and the plane fit, each one launch for all jobs.  max_nb / max_knn:
+// the largest job's k_correspond / k_knn grid.
+static void launch_correspond_batch(lo_batch* b, int nact, int max_nb, int max_knn, int with_stats, int init) {
+    const dim3 blk(kBlock);
+    if (!b->kd) {
+        hipLaunchKernelGGL(k_correspond_b, dim3(max_nb, nact), blk, 0, b->stream, b->d_P, with_stats, init);
+        return;
+    }
+    const int per = std::max(1, std::min(kBatchBrutePerJob, kBatchBruteWGs / nact));
+    const int wgs = static_cast<int>(std::min<long long>(kBatchBruteWGs, static_cast<long long>(nact) * per));
+    hipLaunchKernelGGL(k_knn_b, dim3(max_knn, nact), blk, 0, b->stream, b->d_P, init);
+    hipLaunchKernelGGL(k_knn_brute_b, dim3(wgs), dim3(1024), 0, b->stream, b->d_P, nact, per);
+    hipLaunchKernelGGL(k_plane_b, dim3(max_nb, nact), blk, 0, b->stream, b->d_P, with_stats);
+}
+static int knn_blocks(int n) { return static_cast<int>((static_cast<long long>(n) * kKnnGroup + kBlock - 1) / kBlock); }
+
 extern "C" {
 
 lo_batch* lo_batch_create(lo_ctx* const* ctxs, int count, int* err) {
@@ -168,13 +207,15 @@ lo_batch* lo_batch_create(lo_ctx* const* ctxs, int count, int* err) {
     for (int j = 0; j < count; ++j) {
         const lo_ctx* c = ctxs[j];
         if (!c) return fail(LO_ERR_ARG, "null context");
-        if (c->kd) return fail(LO_ERR_ARG, "batched optimize needs surfel-mode contexts");
+        if (c->kd != ctxs[0]->kd)
+            return fail(LO_ERR_ARG, "surfel-mode and KDTree-mode contexts mixed: one batch has one correspondence mode");
         if (c->device != ctxs[0]->device) return fail(LO_ERR_ARG, "contexts on different devices");
         if (c->cfg.max_iterations != ctxs[0]->cfg.max_iterations) return fail(LO_ERR_ARG, "max_iterations differ");
         for (int k = 0; k < j; ++k) if (ctxs[k] == c) return fail(LO_ERR_ARG, "a context appears twice");
     }
     lo_batch* b = new lo_batch();
     b->ctx.assign(ctxs, ctxs + count);
+    b->kd = ctxs[0]->kd;
     b->device = ctxs[0]->device;
     b->max_iters = ctxs[0]->cfg.max_iterations;
     b->pko_max = kPkoMaxWGs;
@@ -229,16 +270,19 @@ int lo_batch_optimize_async(lo_batch* b, const float* const* d_pts, const size_t
     }
     std::memcpy(b->T_in.data(), T_init, sizeof(float) * 12 * B);
     b->act.clear();
-    int max_nb = 1, max_acc = 1, n_max_ex = 1;
+    b->act_pts.clear();
+    int max_nb = 1, max_acc = 1, n_max_ex = 1, max_knn = 1;
     bool same = true;
     // job order in the device params: the fast-mode jobs, then the reference-exact ones (both in lockstep), then the
     // exact jobs too large for the one-workgroup scale (kExactMergeMax): those run their context's own exact GN loop
+    // (and so does a KDTree job whose grid is the all-pairs form, which has no batched search)
     std::vector<int> fast, exl, ex;
     for (int j = 0; j < B; ++j) {
         b->n[j] = n[j];
         if (n[j] == 0) continue;
         lo_ctx* c = b->ctx[j];
-        if (!c->exact) fast.push_back(j);
+        if (c->kd && c->grid.all) ex.push_back(j);
+        else if (!c->exact) fast.push_back(j);
         else if (n[j] <= static_cast<size_t>(kExactMergeMax)) exl.push_back(j);
         else ex.push_back(j);
     }
@@ -257,7 +301,10 @@ int lo_batch_optimize_async(lo_batch* b, const float* const* d_pts, const size_t
                 max_acc = std::max(max_acc, P.nb_acc);
             }
             max_nb = std::max(max_nb, P.nb);
-            const lo_batch::Sig sg{c, c->cfg_gen, pts, P.n, P.tab, P.log2cap, pass};
+            max_knn = std::max(max_knn, knn_blocks(P.n));
+            const lo_batch::Sig sg{c, c->cfg_gen, pts, P.n, P.tab, P.log2cap, pass, P.kd_pts, P.kd_start, P.kd_m,
+                                   P.kd_nodes != nullptr, {P.kd_org[0], P.kd_org[1], P.kd_org[2]},
+                                   {P.kd_dim[0], P.kd_dim[1], P.kd_dim[2]}, P.kd_h};
             if (a >= static_cast<int>(b->sig.size()) || !(b->sig[a] == sg)) same = false;
             if (!same) {
                 if (a < static_cast<int>(b->sig.size())) b->sig[a] = sg; else b->sig.push_back(sg);
@@ -265,14 +312,20 @@ int lo_batch_optimize_async(lo_batch* b, const float* const* d_pts, const size_t
             b->h_P[a] = P;
             std::memcpy(b->h_T0 + 12 * a, T_init + 12 * j, sizeof(float) * 12);
             b->act.push_back(j);
+            b->act_pts.push_back(pts);
         }
     }
     const int nact = static_cast<int>(b->act.size());
+    if (b->kd && static_cast<long long>(max_knn) * nact > INT_MAX) {
+        b->err = "KDTree batch: the jobs' search grid exceeds 2^31 workgroups";
+        return LO_ERR_CAPACITY;
+    }
     b->nlock = nact;
     // large exact jobs after the lockstep ones: only their DevState pointer is read (k_export_batch)
     for (int j : ex) {
         b->h_P[b->act.size()] = make_params(b->ctx[j], b->ctx[j]->d_pts, static_cast<int>(n[j]));
         b->act.push_back(j);
+        b->act_pts.push_back((d_pts && d_pts[j]) ? d_pts[j] : b->ctx[j]->d_pts);
     }
     const int ntot = static_cast<int>(b->act.size());
     if (!ex.empty()) same = false;
@@ -284,7 +337,7 @@ int lo_batch_optimize_async(lo_batch* b, const float* const* d_pts, const size_t
     }
     if (!ex.empty()) {
         // large reference-exact jobs run their context's own exact GN loop (the chip-wide sequential-sum
-        // reproductions) on the context stream, ordered after the batch's uploads (lo_batch_optimize copies their
+        // reproductions; a KDTree job on an all-pairs grid its context's own launch sequence) on the context stream, ordered after the batch's uploads (lo_batch_optimize copies their
         // points on the batch stream) and before its record export; the scan pipeline stays off for them, so every
         // launch is on the context stream and the record is final when it ends
         LO_HIP(b, hipEventRecord(b->ev_go, b->stream));
@@ -315,7 +368,7 @@ int lo_batch_optimize_async(lo_batch* b, const float* const* d_pts, const size_t
         const size_t pre_bytes = static_cast<size_t>(max_nb) * sizeof(int);
         const dim3 blk(kBlock);
         for (int it = 0; it < b->max_iters; ++it) {
-            hipLaunchKernelGGL(k_correspond_b, dim3(max_nb, nact), blk, 0, b->stream, b->d_P, it == 0 ? 1 : 0, it == 0 ? 1 : 0);
+            launch_correspond_batch(b, nact, max_nb, max_knn, it == 0 ? 1 : 0, it == 0 ? 1 : 0);
             if (it == 0 && nexl > 0) {
                 launch_exact_scale_cb(b->d_P + nfast, nexl, n_max_ex, b->stream);
                 LO_HIP(b, hipGetLastError());                 // e.g. a dynamic-LDS launch the attribute did not allow
@@ -362,7 +415,34 @@ int lo_batch_result(lo_batch* b, lo_batch_rec* out, double* gpu_ms) {
         std::memset(&R, 0, sizeof(R));
         R.status = LO_INSUFFICIENT;
     }
-    for (size_t a = 0; a < b->act.size(); ++a) out[b->act[a]] = b->h_rec[a];
+    for (size_t a = 0; a < b->act.size(); ++a) {
+        const int j = b->act[a];
+        lo_ctx* c = b->ctx[j];
+        const bool tie = b->h_rec[a].pad != 0.0f;
+        b->h_rec[a].pad = 0.0f;
+        if (tie && c->kd && c->grid_dev && !c->grid.has_order) {
+            // a deciding distance tie was ranked by index (a device-built grid has no kd visit order): as lo_icp_result,
+            // the order built on the host from the grid's own points, then this one job again through its context (its
+            // points are still the caller's), and the record of that run
+            int rc = grid_add_order(c);
+            if (rc != LO_OK) { b->err = std::string("tie re-run: ") + c->err; return rc; }
+            const bool pipe = c->pipe, sync_call = c->sync_call;
+            c->pipe = false;
+            c->sync_call = false;
+            rc = enqueue_optimize(c, b->act_pts[a], b->n[j], b->T_in.data() + 12 * j);
+            c->pipe = pipe;
+            c->sync_call = sync_call;
+            c->pending = false;
+            if (rc != LO_OK) { b->err = std::string("tie re-run: ") + c->err; return rc; }
+            hipLaunchKernelGGL(k_export_batch, dim3(1), dim3(64), 0, c->stream, b->d_P + a, b->d_rec + a);
+            LO_HIP(b, hipGetLastError());
+            LO_HIP(b, hipMemcpyAsync(b->h_rec + a, b->d_rec + a, sizeof(lo_batch_rec), hipMemcpyDeviceToHost, c->stream));
+            LO_HIP(b, hipStreamSynchronize(c->stream));
+            b->h_rec[a].pad = 0.0f;
+            ++c->kd_reruns;
+        }
+        out[j] = b->h_rec[a];
+    }
     for (int j = 0; j < B; ++j)            // optimized_transform = initial unless the GN loop succeeded (:266, :301)
         if (out[j].status != LO_OK) std::memcpy(out[j].pose, b->T_in.data() + 12 * j, sizeof(float) * 12);
     if (gpu_ms) {
@@ -379,13 +459,16 @@ int lo_batch_bench_correspond(lo_batch* b, int reps, float* avg_ms) {
     const int nact = b->nlock;
     if (nact == 0) { b->err = "no lockstep batch has run yet"; return LO_ERR_STATE; }
     LO_HIP(b, hipSetDevice(b->device));
-    int max_nb = 1;
-    for (int a = 0; a < nact; ++a) max_nb = std::max(max_nb, b->h_P[a].nb);
-    const dim3 grid(max_nb, nact), blk(kBlock);
-    // every job back at its initial pose with a fresh GN state (init launch), then reps plain launches
-    hipLaunchKernelGGL(k_correspond_b, grid, blk, 0, b->stream, b->d_P, 1, 1);
+    int max_nb = 1, max_knn = 1;
+    for (int a = 0; a < nact; ++a) {
+        max_nb = std::max(max_nb, b->h_P[a].nb);
+        max_knn = std::max(max_knn, knn_blocks(b->h_P[a].n));
+    }
+    // every job back at its initial pose with a fresh GN state (init launch), then reps plain launches (a KDTree
+    // batch: the stage's three launches each time)
+    launch_correspond_batch(b, nact, max_nb, max_knn, 1, 1);
     LO_HIP(b, hipEventRecord(b->ev0, b->stream));
-    for (int r = 0; r < reps; ++r) hipLaunchKernelGGL(k_correspond_b, grid, blk, 0, b->stream, b->d_P, 0, 0);
+    for (int r = 0; r < reps; ++r) launch_correspond_batch(b, nact, max_nb, max_knn, 0, 0);
     LO_HIP(b, hipEventRecord(b->ev1, b->stream));
     LO_HIP(b, hipGetLastError());
     LO_HIP(b, hipEventSynchronize(b->ev1));

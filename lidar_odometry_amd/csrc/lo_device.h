@@ -523,6 +523,23 @@ __device__ __forceinline__ T wave_sum(T v) {
     return v;
 }
 
+// XCD-aware block order: the hardware hands consecutive workgroups to the 8 XCDs round-robin; logical block
+// xcd_block(h) gives XCD x (= h % 8) one contiguous run of the scan's blocks, so spatially coherent points (scans in
+// acquisition order) probe the same surfel-table lines through one L2 instead of eight.  A bijection on [0, nb).
+__device__ __forceinline__ int xcd_block(int h, int nb) {
+    constexpr int kXcd = 8;
+    const int q = nb / kXcd, r = nb % kXcd, x = h % kXcd, k = h / kXcd;
+    return x < r ? x * (q + 1) + k : r * (q + 1) + (x - r) * q + k;
+}
+
+// The KDTree path's unresolved queries (lo_kdtree.hip): a wave per query (k_knn_brute_w) over a small grid without the
+// kd visit order, else a 1024-thread workgroup per query (k_knn_brute, which also ranks deciding ties in the visit order
+// when it is built) -- one rule for launch_brute and the batched pass (k_knn_brute_b).
+constexpr int kBruteWaveMaxM = 16384;   // k_knn_brute_w up to this many grid points (<= 256 per lane)
+__host__ __device__ inline bool brute_wave_form(const void* kd_nodes, int kd_m) {
+    return !kd_nodes && kd_m <= kBruteWaveMaxM;
+}
+
 // Points of this scan: the host count, or the device voxel filter's count (lo_vfilter.hip) when the scan was
 // filtered on the device -- grids are then sized for the upper bound and lanes past the count idle.
 __device__ __forceinline__ int scan_n(const KParams& P) { return P.n_dev ? *P.n_dev : P.n; }

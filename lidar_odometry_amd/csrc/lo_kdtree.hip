@@ -191,12 +191,13 @@ __device__ __forceinline__ float seed_bound(const KParams& P, int i, float qx, f
 
 constexpr int kKnnRowsMax = 4;          // rows of one round per lane: r = 3 has 49 rows over 16 lanes
 
-__device__ __forceinline__ void knn_body(const KParams& P, const float (&T)[12], bool seed) {
+// blk: the launch's block index within this scan (blockIdx.x, or the job's share of a batched grid).
+__device__ __forceinline__ void knn_body(const KParams& P, const float (&T)[12], bool seed, int blk) {
     // kKnnGroup consecutive lanes (one DPP row) share one query: lane g takes rows g, g + 16, ... of each round.
     // The first round scans the whole 3x3x3 cube (the r = 0 cell alone almost never certifies: its faces are
     // < h / 2 away while the 5th neighbour of a surface sample is ~h); later rounds scan the shell r.  A lane's
     // cell-range bounds for the round are loaded together, then its ranges are scanned 8 points at a time.
-    const int gi = blockIdx.x * kBlock + threadIdx.x;
+    const int gi = blk * kBlock + threadIdx.x;
     const int i = gi / kKnnGroup, g = gi % kKnnGroup;
     if (i >= scan_n(P)) return;                              // whole groups leave together
     int32_t* out = P.kd_nbr + 5 * static_cast<size_t>(i);
@@ -283,7 +284,7 @@ __global__ __launch_bounds__(kBlock) void k_knn(KParams P) {
     if (!P.init && P.st->done) return;
     float T[12];
     scan_pose(P, P.init, blockIdx.x, T);
-    knn_body(P, T, !P.init);
+    knn_body(P, T, !P.init, blockIdx.x);
 }
 
 // The solve of GN iteration it fused with the kNN search of iteration it + 1 (small scans with PKO; the
@@ -318,7 +319,7 @@ __global__ __launch_bounds__(kBlock) void k_solve_knn(KParams P, int it) {
     float T[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) T[k] = s_T[k];
-    knn_body(P, T, true);
+    knn_body(P, T, true, blockIdx.x);
 }
 
 // The KDTree counterpart of k_pick_correspond (reference-exact mode): the record of the candidate the PKO launch
@@ -331,7 +332,7 @@ __global__ __launch_bounds__(kBlock) void k_pick_knn(KParams P, int it) {
     float T[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) T[k] = s_rec[k];
-    knn_body(P, T, true);
+    knn_body(P, T, true, blockIdx.x);
 }
 
 // ====================================================================================================
@@ -441,11 +442,13 @@ __device__ __forceinline__ Top5 brute_query_ex(const KParams& P, const KnnQ& Q, 
     return t;
 }
 
-__global__ __launch_bounds__(kBruteThreads) void k_knn_brute(KParams P) {
+// The scan's unresolved queries first, first + stride, ... by this workgroup (uniform arguments: every thread of the
+// workgroup walks the same queries).
+__device__ __forceinline__ void brute_body(const KParams& P, unsigned first, unsigned stride) {
     DevState* st = P.st;
     if (st->done) return;
     const unsigned nu = st->kd_unres_n;
-    if (blockIdx.x >= nu) return;
+    if (first >= nu) return;
     constexpr int kW = kBruteThreads / 64;
     __shared__ float s_d[kW][5];
     __shared__ int s_id[kW][5];
@@ -460,7 +463,7 @@ __global__ __launch_bounds__(kBruteThreads) void k_knn_brute(KParams P) {
     float T[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) T[k] = st->pose[k];
-    for (unsigned u = blockIdx.x; u < nu; u += gridDim.x) {
+    for (unsigned u = first; u < nu; u += stride) {
         const int i = P.kd_unres[u];
         float qx, qy, qz;
         transform_pt(T, P.pts[3 * i], P.pts[3 * i + 1], P.pts[3 * i + 2], qx, qy, qz);
@@ -491,24 +494,25 @@ __global__ __launch_bounds__(kBruteThreads) void k_knn_brute(KParams P) {
     }
 }
 
+__global__ __launch_bounds__(kBruteThreads) void k_knn_brute(KParams P) { brute_body(P, blockIdx.x, gridDim.x); }
+
 // k_knn_brute_w: the same answers by one wave per unresolved query, for a grid of at most 16k points built without the
 // kd visit order (the loop-closure ICP's matched keyframe cloud, a device-built map grid): no LDS, no barrier and no
 // call into the visit-order walk (whose call frame puts k_knn_brute on scratch memory), so a launch with nothing to do
 // costs what an empty launch costs, and a few dozen queries run side by side.  A deciding tie is ranked by index and
 // flagged (DevState::kd_tie) for the host's rerun with the order, as k_knn_brute does without one.
-__global__ __launch_bounds__(kBlock) void k_knn_brute_w(KParams P) {
+// This wave takes the scan's unresolved queries w0, w0 + stride, ...
+__device__ __forceinline__ void brute_w_body(const KParams& P, unsigned w0, unsigned stride) {
     DevState* st = P.st;
     if (st->done) return;
     const unsigned nu = st->kd_unres_n;
-    constexpr int kWpb = kBlock / kWave;
     const int lane = threadIdx.x & 63;
-    const unsigned w0 = blockIdx.x * kWpb + (threadIdx.x >> 6);
     if (w0 >= nu) return;
     float T[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) T[k] = st->pose[k];
     const KnnQ Q0{{0.0f, 0.0f, 0.0f}, nullptr, nullptr};
-    for (unsigned u = w0; u < nu; u += gridDim.x * kWpb) {
+    for (unsigned u = w0; u < nu; u += stride) {
         const int i = P.kd_unres[u];
         float qx, qy, qz;
         transform_pt(T, P.pts[3 * i], P.pts[3 * i + 1], P.pts[3 * i + 2], qx, qy, qz);
@@ -537,6 +541,11 @@ __global__ __launch_bounds__(kBlock) void k_knn_brute_w(KParams P) {
             else for (int k = 0; k < 5; ++k) out[k] = t.pos[k];
         }
     }
+}
+
+__global__ __launch_bounds__(kBlock) void k_knn_brute_w(KParams P) {
+    constexpr int kWpb = kBlock / kWave;
+    brute_w_body(P, blockIdx.x * kWpb + (threadIdx.x >> 6), gridDim.x * kWpb);
 }
 
 // ====================================================================================================
@@ -781,11 +790,11 @@ __device__ __forceinline__ void smallest_eigvec3d(double (&A)[3][3], double (&v)
     for (int k = 0; k < 3; ++k) v[k] = (mi == 0) ? V[k][0] : (mi == 1 ? V[k][1] : V[k][2]);
 }
 
-__global__ __launch_bounds__(kBlock) void k_plane(KParams P, int with_stats) {
+__device__ __forceinline__ void plane_body(const KParams& P, int with_stats, int blk) {
     DevState* st = P.st;
     if (st->done) return;
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {                        // k_knn_brute has drained the list
+    const int i = blk * kBlock + threadIdx.x;
+    if (blk == 0 && threadIdx.x == 0) {                        // k_knn_brute has drained the list
         st->dbg[15] = st->kd_unres_n;                                 // last unresolved count (lo_debug_counters)
         st->kd_unres_n = 0;
     }
@@ -863,7 +872,63 @@ __global__ __launch_bounds__(kBlock) void k_plane(KParams P, int with_stats) {
         P.slot[i] = valid ? i : -1;
         if (P.res_dbg) P.res_dbg[i] = valid ? dist : 0.0;
     }
-    corr_epilogue(P, valid, dist, with_stats, blockIdx.x);
+    corr_epilogue(P, valid, dist, with_stats, blk);
+}
+
+__global__ __launch_bounds__(kBlock) void k_plane(KParams P, int with_stats) { plane_body(P, with_stats, blockIdx.x); }
+
+// ====================================================================================================
+// Batched launches (lo_batch_*, KDTree-mode contexts): the counterparts of k_correspond_b.  The bodies above run per
+// job on the job's own KParams (PB[job], uniform per workgroup: scalar loads of the fields a body reads), so a job's
+// neighbours, planes, residuals and ballots are what its context's own launches write.
+// ====================================================================================================
+// The (block, job) grid linearised in XCD-aware order, as k_correspond_b: an XCD takes whole jobs, so a job's grid cells
+// and points are cached by one L2.
+__device__ __forceinline__ void batch_block(int& job, int& blk) {
+    const int gx = static_cast<int>(gridDim.x);
+    const int lin = xcd_block(static_cast<int>(blockIdx.x + blockIdx.y * gridDim.x), gx * static_cast<int>(gridDim.y));
+    job = lin / gx;
+    blk = lin - job * gx;
+}
+
+// k_knn per job: the grid is sized for the largest job (kKnnGroup lanes per query), a job's surplus blocks leave before
+// touching any of its buffers, a finished job leaves at once.  The unresolved-query counter is the job's own
+// (DevState::kd_unres_n, zeroed by the job's block 0 of k_plane_b after the unresolved pass has drained it).
+__global__ __launch_bounds__(kBlock) void k_knn_b(const KParams* __restrict__ PB, int init) {
+    int job, blk;
+    batch_block(job, blk);
+    const KParams& P = PB[job];
+    if (blk >= (P.n * kKnnGroup + kBlock - 1) / kBlock) return;
+    if (!init && P.st->done) return;
+    float T[12];
+    scan_pose(P, init, blk, T);
+    knn_body(P, T, !init, blk);
+}
+
+// The unresolved queries of every job in one launch: `per` workgroups per job, strided over the (job, workgroup) pairs
+// by a grid the host bounds (a job's unresolved list is short or empty, so B jobs do not need B x kBruteBlocks
+// workgroups).  The form is the job's, by launch_brute's rule: a wave per query (the 16 waves of the workgroup take 16
+// queries side by side) or the whole workgroup per query with the visit-order ranking of deciding ties.
+__global__ __launch_bounds__(kBruteThreads) void k_knn_brute_b(const KParams* __restrict__ PB, int njobs, int per) {
+    constexpr int kW = kBruteThreads / kWave;
+    const unsigned wid = threadIdx.x >> 6;
+    const int g = static_cast<int>(gridDim.x);
+    for (int w = xcd_block(static_cast<int>(blockIdx.x), g); w < njobs * per; w += g) {
+        const int job = w / per;
+        const unsigned sub = static_cast<unsigned>(w - job * per);
+        const KParams& P = PB[job];
+        if (brute_wave_form(P.kd_nodes, P.kd_m)) brute_w_body(P, sub * kW + wid, static_cast<unsigned>(per) * kW);
+        else brute_body(P, sub, static_cast<unsigned>(per));
+    }
+}
+
+// k_plane per job, on the grid of k_correspond_b (a block per kBlock points of the largest job)
+__global__ __launch_bounds__(kBlock) void k_plane_b(const KParams* __restrict__ PB, int with_stats) {
+    int job, blk;
+    batch_block(job, blk);
+    const KParams& P = PB[job];
+    if (blk >= P.nb) return;
+    plane_body(P, with_stats, blk);
 }
 
 // optimize_loop's inlier ratio (:206-238): the curr cloud at the converged pose (t + R p, :220-221), each point an

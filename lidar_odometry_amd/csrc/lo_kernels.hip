@@ -60,15 +60,6 @@ __device__ __forceinline__ void correspond_body(const KParams& P, int with_stats
     }
 }
 
-// XCD-aware block order: the hardware hands consecutive workgroups to the 8 XCDs round-robin; logical block
-// xcd_block(h) gives XCD x (= h % 8) one contiguous run of the scan's blocks, so spatially coherent points (scans in
-// acquisition order) probe the same surfel-table lines through one L2 instead of eight.  A bijection on [0, nb).
-__device__ __forceinline__ int xcd_block(int h, int nb) {
-    constexpr int kXcd = 8;
-    const int q = nb / kXcd, r = nb % kXcd, x = h % kXcd, k = h / kXcd;
-    return x < r ? x * (q + 1) + k : r * (q + 1) + (x - r) * q + k;
-}
-
 __global__ __launch_bounds__(kBlock) void k_correspond(KParams P, int with_stats) {
     correspond_body(P, with_stats, P.init, xcd_block(blockIdx.x, gridDim.x));
 }
@@ -522,6 +513,9 @@ __global__ void k_export_batch(const KParams* __restrict__ PB, lo_batch_rec* out
     if (t == 15) R.alpha = st->alpha;
     if (t == 16) R.initial_cost = st->iter > 0 ? st->logs[0].cost : 0.0f;
     if (t == 17) R.final_cost = st->iter > 0 ? st->logs[min(st->iter, LO_MAX_ITERS) - 1].cost : 0.0f;
+    // KDTree jobs: a deciding distance tie was ranked by index (DevState::kd_tie); lo_batch_result reads the flag from
+    // the record's padding word and hands the caller 0 there
+    if (t == 18) R.pad = st->kd_tie ? 1.0f : 0.0f;
 }
 
 }  // namespace lo

@@ -34,6 +34,9 @@ __global__ void k_knn_reset(KParams P);
 __global__ void k_plane(KParams P, int with_stats);
 __global__ void k_inlier(KParams P);
 __global__ void k_correspond_b(const KParams* PB, int with_stats, int init);
+__global__ void k_knn_b(const KParams* PB, int init);
+__global__ void k_knn_brute_b(const KParams* PB, int njobs, int per);
+__global__ void k_plane_b(const KParams* PB, int with_stats);
 template <int NW, bool ONE_WAVE> __global__ void k_pko_tb(const KParams* PB, int it);
 __global__ void k_accumulate_b(const KParams* PB, int it);
 template <bool SOLVE> __global__ void k_accumulate_b1(const KParams* PB, int it);

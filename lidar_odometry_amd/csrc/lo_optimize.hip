@@ -87,12 +87,11 @@ static bool pipe_flagged(const lo_ctx* c) { return c->h_broken && __atomic_load_
 // fallback + plane fit.  P0 carries init = 1 on a scan's first iteration.
 static constexpr int kBruteBlocks = 64;      // k_knn_brute workgroups (grid-strided over the unresolved list)
 static constexpr int kBruteWaveBlocks = 256; // k_knn_brute_w: 4 queries in flight per workgroup
-static constexpr int kBruteWaveMaxM = 16384; // k_knn_brute_w up to this many grid points (<= 256 per lane)
 
 // The unresolved queries: a wave per query (k_knn_brute_w) over a small grid without the kd visit order, else a
 // 1024-thread workgroup per query (k_knn_brute, which also ranks deciding ties in the visit order when it is built).
 void launch_brute(lo_ctx* c, const KParams& P) {
-    if (!P.kd_nodes && P.kd_m <= kBruteWaveMaxM) hipLaunchKernelGGL(k_knn_brute_w, dim3(kBruteWaveBlocks), dim3(kBlock), 0, c->stream, P);
+    if (brute_wave_form(P.kd_nodes, P.kd_m)) hipLaunchKernelGGL(k_knn_brute_w, dim3(kBruteWaveBlocks), dim3(kBlock), 0, c->stream, P);
     else hipLaunchKernelGGL(k_knn_brute, dim3(kBruteBlocks), dim3(1024), 0, c->stream, P);
 }
 

@@ -414,7 +414,13 @@ class BatchResult:
 class BatchOptimizer:
     """Scan-parallel optimize on one GPU (lo_batch_*): B independent contexts -- B sequences, each with its own
     map and GN state -- run IterativeClosestPointOptimizer::optimize in lockstep, one launch per kernel per GN
-    iteration for all of them.  Each job's result equals ``optimizers[j].optimize`` on the same input."""
+    iteration for all of them.  Each job's result equals ``optimizers[j].optimize`` on the same input.
+
+    Both correspondence modes are supported, one per batch: the optimizers are all surfel-mode or all KDTree-mode
+    (``use_surfel_correspondence=False``; a mixed list raises).  ``optimize(voxel_maps, ...)`` uploads a KDTree
+    context's map as its L0 point cloud (``set_map_points``), a surfel context's as its surfel table.  A KDTree job
+    whose grid was built on the device (``DeviceVoxelMap.sync_points``) and that meets a deciding distance tie is run
+    again through its own context inside ``result()``, as ``optimize`` does (``lo_kd_reruns``)."""
 
     def __init__(self, optimizers):
         self.optimizers = list(optimizers)
