@@ -249,7 +249,10 @@ int lo_bench_correspond_rr(lo_ctx* const* ctxs, const float* const* d_pts, const
  * reference-exact mode (lo_set_exact) runs its own exact GN loop on its context stream inside the batch call (the
  * sequential-sum reproductions have no lockstep form), ordered after the batch's uploads and before its record
  * export, bit-identical to its lo_icp_optimize.  The batch runs on its own stream; the contexts must be idle while
- * it runs and each context's lo_icp_result() is not valid for a batched scan (use lo_batch_result). */
+ * it runs and each context's lo_icp_result() is not valid for a batched scan (use lo_batch_result).
+ * The sequences' maps follow their keyframes through lo_batch_update_maps / lo_batch_maps_status (lo_map.h: the device
+ * maps' update for all active jobs in one set of launches on the batch stream), and lo_odom_batch_* (lo_odometry.h)
+ * is the whole frame loop for B sequences built on these entry points. */
 typedef struct lo_batch lo_batch;
 typedef struct lo_batch_rec {
     float  pose[12];       /* optimized pose (T_init when status != LO_OK, as lo_icp_optimize) */

@@ -119,6 +119,28 @@ size_t      lo_devmap_get_l0(lo_devmap* m, int32_t* keys, float* xyz, int32_t* p
 size_t      lo_devmap_get_l1(lo_devmap* m, int32_t* keys, uint8_t* has_surfel, float* normals, float* centroids,
                              float* planarity, int32_t* child_counts, int32_t* children, size_t cap);
 
+/* ---- the maps of a batch (lo_icp.h lo_batch_*) ----
+ * UpdateVoxelMap for the keyframes of a batch: for every job j with active[j] != 0, what
+ * lo_devmap_update_from_scan(maps[j], T + 12*j, max_distance) does, in one set of launches for all active jobs on the
+ * batch stream (24 launches, blockIdx.y = active job; the single-workgroup phases run one workgroup per job).
+ * maps[j] was created on the batch's context j (else LO_ERR_ARG; entries of inactive jobs are not read).  Each job
+ * reads its own context's device-filtered scan and device count (lo_batch_filter_raw* or lo_voxel_filter_gpu left
+ * them there), and its map afterwards equals the single call's bit for bit; a job whose count is 0 changes nothing; a
+ * job that overflows a capacity aborts its own update and sets its own error bits.  Maps of different capacities may
+ * share a batch; single and batched updates may alternate on one map.  Enqueues and returns; the contexts must be
+ * idle, as for every batch call, and whatever the next batch call runs on a context stream is ordered behind the
+ * update.  Before a map is used through its own context (lo_devmap_counts, lo_devmap_update...), wait for the batch
+ * stream: lo_batch_maps_status does.  A context whose table was replaced since the last update (an unrelated
+ * lo_map_set_surfels, say) has it emptied and refilled on its own stream before this update; the call first waits
+ * on the host for the batch's previous update.  LO_ERR_STATE while a batch optimize is in flight. */
+int         lo_batch_update_maps(lo_batch* b, lo_devmap* const* maps, const unsigned char* active, const float* T,
+                                 double max_distance);
+/* Error bits of all jobs' maps in one copy (synchronises the batch stream): rc[j] (nullable) = LO_OK or
+ * LO_ERR_CAPACITY; returns LO_OK when every job is LO_OK, else LO_ERR_CAPACITY (lo_batch_last_error names the first
+ * such job, and each such map's lo_devmap_last_error is set).  maps[j] may be NULL for a job that has no map: it
+ * reports LO_OK. */
+int         lo_batch_maps_status(lo_batch* b, lo_devmap* const* maps, int* rc);
+
 #ifdef __cplusplus
 }
 #endif

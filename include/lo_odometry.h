@@ -156,6 +156,34 @@ int       lo_odom_build_map(lo_odometry* o, float voxel_size, size_t* out_n);
 long long lo_odom_map_points(lo_odometry* o, float* out_xyz, size_t cap);
 int       lo_odom_save_map_ply(lo_odometry* o, const char* path, float voxel_size);
 
+/* ---- the frame loop for B sequences on one GPU ----
+ * lo_odom_process for `count` independent sequences in lockstep, joined from the batch's pieces (lo_icp.h lo_batch_*,
+ * lo_map.h lo_batch_update_maps): `count` contexts, one lo_batch, one device map per context (max_l0 L0 voxels each)
+ * and one pose bookkeeping per sequence.  Per call: one batched voxel filter (lo_batch_filter_raw_host), every
+ * sequence's guess, one batched optimize (lo_batch_optimize_async + lo_batch_result), every sequence's pose update and
+ * keyframe test, and one batched map update (lo_batch_update_maps) over the sequences that made a keyframe.  The first
+ * call makes every sequence with a non-empty filtered scan a keyframe at its initial pose; a sequence whose first scan
+ * filtered to nothing takes lo_odom_process's early return on every later call.  Sequence j's poses, keyframe flags,
+ * iteration counts and guesses equal, bit for bit, those of a lo_odometry fed sequence j alone with the same config
+ * and mode.  The maps' error bits are read once per call for all sequences, after the next call's ICP result (an
+ * aborted update is reported -- LO_ERR_CAPACITY, the call returns before the poses are committed -- at the first call
+ * after its keyframe); lo_odom_batch_flush reads them at once.
+ * Surfel mode only: a KDTree config (use_surfel_correspondence = 0) is refused with LO_ERR_ARG (its per-context
+ * lo_devmap_sync_points has no batched form); lo_odom_batch_last_error(NULL) says why the calling thread's last create failed.  No loop
+ * closure.  info[j].device_ms is the whole batch's optimize; info[j].map_ms the batched update's enqueue. */
+typedef struct lo_odom_batch lo_odom_batch;
+lo_odom_batch* lo_odom_batch_create(const lo_odom_config* cfg, int count, int device, size_t max_l0, int* err);
+void        lo_odom_batch_destroy(lo_odom_batch* o);
+const char* lo_odom_batch_last_error(const lo_odom_batch* o);
+int lo_odom_batch_set_initial_pose(lo_odom_batch* o, int job, const float T[12]);
+int lo_odom_batch_set_exact(lo_odom_batch* o, int enable);
+/* One raw scan per sequence (host memory; pinned memory is read in place) -> one pose per sequence (count x 12) and,
+ * nullable, count lo_odom_frame.  Returns LO_OK, or the first negative error; per-job LO_OK / LO_INSUFFICIENT is in
+ * info[j].status. */
+int lo_odom_batch_process(lo_odom_batch* o, const float* const* raw, const size_t* n, float* T_out, lo_odom_frame* info);
+int lo_odom_batch_flush(lo_odom_batch* o);     /* lo_batch_maps_status of the last keyframes */
+size_t lo_odom_batch_keyframe_count(const lo_odom_batch* o, int job);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,11 +40,14 @@ EXPORTED_SYMBOLS = (
     "lo_map_set_from_voxelmap", "lo_map_sync_voxelmap", "lo_voxelmap_apply_transform", "lo_map_patch_surfels", "lo_voxel_filter",
     "lo_voxelmap_set_device_fit", "lo_devmap_create", "lo_devmap_destroy", "lo_devmap_last_error", "lo_devmap_update",
     "lo_devmap_update_from_scan", "lo_devmap_apply_transform", "lo_devmap_counts", "lo_devmap_status", "lo_devmap_status_async", "lo_devmap_status_poll", "lo_devmap_sync_points", "lo_kd_reruns", "lo_devmap_get_l0", "lo_devmap_get_l1",
+    "lo_batch_update_maps", "lo_batch_maps_status",
     # include/lo_odometry.h
     "lo_odom_config_default_kitti", "lo_odom_create", "lo_odom_destroy", "lo_odom_last_error", "lo_odom_set_initial_pose",
     "lo_odom_process", "lo_odom_keyframe_count", "lo_odom_map_surfels", "lo_odom_set_exact", "lo_odom_flush",
     "lo_loop_config_default", "lo_odom_enable_loop_closure", "lo_odom_last_loop", "lo_odom_loop_count",
     "lo_odom_keyframe_poses", "lo_odom_build_map", "lo_odom_map_points", "lo_odom_save_map_ply",
+    "lo_odom_batch_create", "lo_odom_batch_destroy", "lo_odom_batch_last_error", "lo_odom_batch_set_initial_pose",
+    "lo_odom_batch_set_exact", "lo_odom_batch_process", "lo_odom_batch_flush", "lo_odom_batch_keyframe_count",
     # include/lo_io.h
     "lo_load_kitti_bin", "lo_load_ply", "lo_kitti_pose_line", "lo_save_trajectory_kitti", "lo_save_ply",
     # include/lo_pgo.h
@@ -304,6 +307,20 @@ def lib():
     L.lo_batch_filter_ms.argtypes = [vp]
     L.lo_batch_optimize_raw.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_int, C.c_float, fp,
                                         C.POINTER(LoBatchRec), C.POINTER(C.c_size_t)]
+    L.lo_batch_update_maps.argtypes = [vp, C.POINTER(vp), u8p, fp, C.c_double]
+    L.lo_batch_maps_status.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int)]
+    L.lo_odom_batch_create.restype = vp
+    L.lo_odom_batch_create.argtypes = [C.POINTER(LoOdomConfig), C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_int)]
+    L.lo_odom_batch_destroy.restype = None
+    L.lo_odom_batch_destroy.argtypes = [vp]
+    L.lo_odom_batch_last_error.restype = C.c_char_p
+    L.lo_odom_batch_last_error.argtypes = [vp]
+    L.lo_odom_batch_set_initial_pose.argtypes = [vp, C.c_int, fp]
+    L.lo_odom_batch_set_exact.argtypes = [vp, C.c_int]
+    L.lo_odom_batch_process.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), fp, C.POINTER(LoOdomFrame)]
+    L.lo_odom_batch_flush.argtypes = [vp]
+    L.lo_odom_batch_keyframe_count.restype = C.c_size_t
+    L.lo_odom_batch_keyframe_count.argtypes = [vp, C.c_int]
     L.lo_voxelmap_create.restype = vp
     L.lo_voxelmap_create.argtypes = [C.c_float, C.c_int, C.c_float, C.c_int]
     L.lo_voxelmap_destroy.argtypes = [vp]

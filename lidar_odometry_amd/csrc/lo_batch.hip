@@ -82,7 +82,21 @@ struct lo_batch {
     hipEvent_t evf0 = nullptr, evf1 = nullptr;
     bool filt_timed = false;
     bool pending = false;
+    // lo_batch_update_maps (lo_devmap.hip): its per-batch state, and how to free it
+    void* map_state = nullptr;
+    void (*map_state_release)(void*) = nullptr;
 };
+
+namespace lo {
+BatchView batch_view(lo_batch* b) {
+    return BatchView{b->ctx.data(), static_cast<int>(b->ctx.size()), b->device, b->stream, b->pending};
+}
+void batch_set_error(lo_batch* b, const char* msg) { b->err = msg; }
+void** batch_map_state(lo_batch* b, void (*release)(void*)) {
+    b->map_state_release = release;
+    return &b->map_state;
+}
+}  // namespace lo
 
 static int batch_alloc(lo_batch* b) {
     const size_t B = b->ctx.size();
@@ -238,6 +252,7 @@ void lo_batch_destroy(lo_batch* b) {
     if (!b) return;
     (void)hipSetDevice(b->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
+    if (b->map_state && b->map_state_release) b->map_state_release(b->map_state);
     if (b->ev0) (void)hipEventDestroy(b->ev0);
     if (b->ev1) (void)hipEventDestroy(b->ev1);
     if (b->ev_go) (void)hipEventDestroy(b->ev_go);

@@ -30,6 +30,8 @@ int ctx_fit_results(lo_ctx* c, uint64_t ticket, FitResult* out, size_t n_jobs);
 // context stream) unless it is still the generation the map reserved last time; *gen changes whenever the table was
 // emptied, so the map refills it.  Any other upload to the context bumps the generation.
 int ctx_reserve_table(lo_ctx* c, size_t min_slots, void** tab, uint32_t* log2cap, uint64_t* gen);
+// Whether ctx_reserve_table(c, min_slots, ...) would hand back the table as it is (no emptying, no new generation).
+bool ctx_table_current(const lo_ctx* c, size_t min_slots);
 // The device-filtered scan of the last lo_icp_optimize_raw / lo_voxel_filter_gpu: device points and the device
 // count (stream-ordered; no sync).
 int ctx_filtered_device(lo_ctx* c, const float** d_pts, const int** d_n);
@@ -40,4 +42,21 @@ int ctx_filtered_device(lo_ctx* c, const float** d_pts, const int** d_n);
 // order is built: a query that meets a deciding distance tie flags it, and lo_icp_result rebuilds the grid with the
 // order on the host and re-runs that scan (rare: equal distances between distinct centroids).
 int ctx_grid_from_device(lo_ctx* c, const float* d_xyz, const int* d_count, size_t cap);
+// The host's copy of that scan's count when it is already known without a sync (after lo_batch_filter_raw*, or a
+// collected lo_icp_optimize_raw), else -1.
+long long ctx_filtered_count_known(const lo_ctx* c);
+
+// A batch as the batched map update (lo_devmap.hip: lo_batch_update_maps, lo_batch_maps_status) sees it: its contexts,
+// its stream, whether an optimize is in flight, its error text, and one slot for that update's per-batch state (the
+// device array of map descriptors), freed with the batch through `release`.
+struct BatchView {
+    lo_ctx* const* ctx;
+    int count;
+    int device;
+    void* stream;
+    bool pending;
+};
+BatchView batch_view(lo_batch* b);
+void batch_set_error(lo_batch* b, const char* msg);
+void** batch_map_state(lo_batch* b, void (*release)(void*));
 }  // namespace lo

@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <climits>
 #include <cstdlib>
 #include <cmath>
@@ -312,6 +313,7 @@ __device__ int block_compact(int n, int* out, int* s_w, Pred pred) {
         if (f) out[base + r] = i;
         base += tot;
     }
+    __syncthreads();                                       // out[] is read by other lanes than its writers
     return base;
 }
 
@@ -482,7 +484,7 @@ __device__ void erase_batches(const DM& M, const int* list0, int q0, const int* 
 
 // ---------------------------------------------------------------------------------------------- kernels
 // world points from a device scan: util::transform_point_cloud's order (lo_math.h transform_points)
-__global__ __launch_bounds__(kPar) void k_dm_world(DM M, const float* in, const int* dn, float* out) {
+__device__ __forceinline__ void dm_world_body(const DM& M, const float* in, const int* dn, float* out) {
     if (M.prm_n[1] != 1) return;                         // host-given points: already in place
     const int n = point_count(M, 0, dn);
     if (blockIdx.x == 0 && threadIdx.x == 0) M.prm_n[0] = n;
@@ -495,27 +497,27 @@ __global__ __launch_bounds__(kPar) void k_dm_world(DM M, const float* in, const 
     }
 }
 struct DmParams { float v[16]; int n, from_scan; };
-__global__ void k_dm_setprm(DM M, DmParams P) {
+__device__ __forceinline__ void dm_setprm_body(const DM& M, const DmParams& P) {
     if (threadIdx.x < 16) M.prm[threadIdx.x] = P.v[threadIdx.x];
     if (threadIdx.x == 0) { M.prm_n[0] = P.n; M.prm_n[1] = P.from_scan; }
 }
 
 // prune mark (:146-157): dist^2 = (c - s).squaredNorm() > radius^2 in fp32; per-workgroup counts
-__device__ __forceinline__ void prune_range(int n0, int b, int* lo, int* hi) {
-    const int ch = (n0 + kPruneBlocks - 1) / kPruneBlocks;
+__device__ __forceinline__ void prune_range(int n0, int b, int G, int* lo, int* hi) {
+    const int ch = (n0 + G - 1) / G;
     *lo = min(n0, b * ch);
     *hi = min(n0, *lo + ch);
 }
 // (an empty device-filtered cloud prunes nothing: UpdateVoxelMap returns first, :135-137)
 __device__ __forceinline__ int prune_n0(const DM& M, const int* dn) { return (dn && *dn <= 0) ? 0 : M.cnt[C_N0]; }
-__global__ __launch_bounds__(kPar) void k_dm_prune_mark(DM M, const int* dn) {
+__device__ __forceinline__ void dm_prune_mark_body(const DM& M, const int* dn) {
     __shared__ int s_c;
     const float sx = M.prm[0], sy = M.prm[1], sz = M.prm[2], rsq = M.prm[3];
     if (blockIdx.x == 0 && threadIdx.x == 0) M.cnt[C_REBUILD] = 0;        // the previous update's rebuild ran
     if (threadIdx.x == 0) s_c = 0;
     __syncthreads();
     int lo, hi;
-    prune_range(prune_n0(M, dn), blockIdx.x, &lo, &hi);
+    prune_range(prune_n0(M, dn), blockIdx.x, gridDim.x, &lo, &hi);
     int c = 0;
     for (int i = lo + threadIdx.x; i < hi; i += kPar) {
         const float d0 = M.c0[3 * i] - sx, d1 = M.c0[3 * i + 1] - sy, d2 = M.c0[3 * i + 2] - sz;
@@ -529,7 +531,7 @@ __global__ __launch_bounds__(kPar) void k_dm_prune_mark(DM M, const int* dn) {
     if (threadIdx.x == 0) M.blkcnt[blockIdx.x] = s_c;
 }
 // ordered compaction of the marks: D = doomed positions in L0 order
-__global__ __launch_bounds__(kPar) void k_dm_prune_compact(DM M, const int* dn) {
+__device__ __forceinline__ void dm_prune_compact_body(const DM& M, const int* dn) {
     __shared__ int s_base, s_w[kPar / 64 + 1];
     const int b = blockIdx.x;
     if (threadIdx.x == 0) s_base = 0;
@@ -539,7 +541,7 @@ __global__ __launch_bounds__(kPar) void k_dm_prune_compact(DM M, const int* dn) 
     atomicAdd(&s_base, part);
     __syncthreads();
     int lo, hi;
-    prune_range(prune_n0(M, dn), b, &lo, &hi);
+    prune_range(prune_n0(M, dn), b, gridDim.x, &lo, &hi);
     int base = s_base;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     for (int t = lo; t < hi; t += kPar) {
@@ -555,12 +557,12 @@ __global__ __launch_bounds__(kPar) void k_dm_prune_compact(DM M, const int* dn) 
         base += tot;
         __syncthreads();
     }
-    if (b == kPruneBlocks - 1 && threadIdx.x == 0) M.cnt[C_Q] = base;
+    if (b == static_cast<int>(gridDim.x) - 1 && threadIdx.x == 0) M.cnt[C_Q] = base;
 }
 
 // UnregisterFromParent (:77-97) for the doomed in L0 order, then the L0 erases in that order and the L1 erases in the
 // order the voxels emptied
-__global__ __launch_bounds__(kOrch) void k_dm_unregister(DM M) {
+__device__ __forceinline__ void dm_unregister_body(const DM& M) {
     unsigned long long st_t0 = M.st ? __builtin_amdgcn_s_memtime() : 0ull;
     __shared__ int s_w[64];
     __shared__ int s_sim[8 * kSimLds];
@@ -574,6 +576,7 @@ __global__ __launch_bounds__(kOrch) void k_dm_unregister(DM M) {
         if (k < kKids) M.ulist[static_cast<size_t>(lp) * kKids + k] = j;
         else atomicOr(&M.cnt[C_ERR], E_KIDS);
     }
+    __syncthreads();                                       // every parent's ucnt / ulist complete before lanes read them
     DM_ST(30);
     // one lane per parent (the lane of its first doomed child in list order): its children set's erases in L0 order
     for (int j = threadIdx.x; j < q; j += kOrch) {
@@ -645,7 +648,7 @@ __device__ void dm_keys_one(const DM& M, const float* pts, int i) {
     atomicAdd(&M.tpcnt[s0], 1);
     atomicMin(&M.ttfirst[s1], i);
 }
-__global__ __launch_bounds__(kPar) void k_dm_keys(DM M, const float* pts, int n_host, const int* dn) {
+__device__ __forceinline__ void dm_keys_body(const DM& M, const float* pts, int n_host, const int* dn) {
     const int n = point_count(M, n_host, dn);
     for (int i = blockIdx.x * kPar + threadIdx.x; i < n; i += gridDim.x * kPar) dm_keys_one(M, pts, i);
 }
@@ -682,7 +685,7 @@ __device__ __forceinline__ int npts(const DM& M, int n_host, const int* dn) { re
 
 // (1) per point: the existing voxel of its group (looked up at the group's first point); chunk counts of new groups,
 // group sizes and touched-key first occurrences
-__global__ __launch_bounds__(kPar) void k_dm_a_count(DM M, int n_host, const int* dn) {
+__device__ __forceinline__ void dm_a_count_body(const DM& M, int n_host, const int* dn) {
     __shared__ int s_c[3];
     const int n = npts(M, n_host, dn);
     if (threadIdx.x < 3) s_c[threadIdx.x] = 0;
@@ -707,7 +710,7 @@ __global__ __launch_bounds__(kPar) void k_dm_a_count(DM M, int n_host, const int
     if (threadIdx.x < 3) M.bc[threadIdx.x * kChunk + blockIdx.x] = s_c[threadIdx.x];
 }
 // chunk offsets of three counts (stage 1: new L0 / group lists / touched; stage 2: new L1 / child lists)
-__global__ __launch_bounds__(kOrch) void k_dm_scan3(DM M, int stage) {
+__device__ __forceinline__ void dm_scan3_body(const DM& M, int stage) {
     __shared__ int s_w[64];
     const int t = threadIdx.x;
     int tot[3];
@@ -729,7 +732,7 @@ __global__ __launch_bounds__(kOrch) void k_dm_scan3(DM M, int stage) {
     }
 }
 // (2) ranks: new L0 voxels appended in first-occurrence order, group list offsets, the touched list
-__global__ __launch_bounds__(kPar) void k_dm_a_rank(DM M, int n_host, const int* dn) {
+__device__ __forceinline__ void dm_a_rank_body(const DM& M, int n_host, const int* dn) {
     __shared__ int s_w[kPar / 64];
     if (M.cnt[C_ABORT]) return;
     const int n = npts(M, n_host, dn);
@@ -763,7 +766,7 @@ __global__ __launch_bounds__(kPar) void k_dm_a_rank(DM M, int n_host, const int*
     }
 }
 // (3) the groups' point lists
-__global__ __launch_bounds__(kPar) void k_dm_a_fill(DM M, int n_host, const int* dn) {
+__device__ __forceinline__ void dm_a_fill_body(const DM& M, int n_host, const int* dn) {
     if (M.cnt[C_ABORT]) return;
     const int n = npts(M, n_host, dn);
     for (int i = blockIdx.x * kPar + threadIdx.x; i < n; i += gridDim.x * kPar) {
@@ -772,7 +775,7 @@ __global__ __launch_bounds__(kPar) void k_dm_a_fill(DM M, int n_host, const int*
     }
 }
 // (4) running mean per voxel over its points in point order (fp32, (c n + p) / (n + 1)); one lane per group
-__global__ __launch_bounds__(kPar) void k_dm_a_mean(DM M, const float* pts, int n_host, const int* dn) {
+__device__ __forceinline__ void dm_a_mean_body(const DM& M, const float* pts, int n_host, const int* dn) {
     if (M.cnt[C_ABORT]) return;
     const int n = npts(M, n_host, dn);
     for (int i = blockIdx.x * kPar + threadIdx.x; i < n; i += gridDim.x * kPar) {
@@ -807,7 +810,7 @@ __global__ __launch_bounds__(kPar) void k_dm_a_mean(DM M, const float* pts, int 
     }
 }
 // (5) RegisterToParent (:69-75) for the new L0 voxels in creation order: group them by parent
-__global__ __launch_bounds__(kPar) void k_dm_r_group(DM M) {
+__device__ __forceinline__ void dm_r_group_body(const DM& M) {
     if (M.cnt[C_ABORT]) return;
     const int nnew = M.cnt[C_NNEW], n0 = M.cnt[C_N0];
     for (int r = blockIdx.x * kPar + threadIdx.x; r < nnew; r += gridDim.x * kPar) {
@@ -818,7 +821,7 @@ __global__ __launch_bounds__(kPar) void k_dm_r_group(DM M) {
     }
 }
 // (6) each parent (at its first new child): existing L1 voxel or not; chunk counts of new L1s and child lists
-__global__ __launch_bounds__(kPar) void k_dm_r_count(DM M) {
+__device__ __forceinline__ void dm_r_count_body(const DM& M) {
     __shared__ int s_c[2];
     if (M.cnt[C_ABORT]) return;
     const int nnew = M.cnt[C_NNEW];
@@ -841,7 +844,7 @@ __global__ __launch_bounds__(kPar) void k_dm_r_count(DM M) {
     if (threadIdx.x < 3) M.bc[threadIdx.x * kChunk + blockIdx.x] = threadIdx.x < 2 ? s_c[threadIdx.x] : 0;
 }
 // (7) new L1 voxels appended in first-child order; child-list offsets
-__global__ __launch_bounds__(kPar) void k_dm_r_rank(DM M) {
+__device__ __forceinline__ void dm_r_rank_body(const DM& M) {
     __shared__ int s_w[kPar / 64];
     if (M.cnt[C_ABORT]) return;
     const int nnew = M.cnt[C_NNEW], n1 = M.cnt[C_N1];
@@ -872,7 +875,7 @@ __global__ __launch_bounds__(kPar) void k_dm_r_rank(DM M) {
         b0 += t0; b1 += t1;
     }
 }
-__global__ __launch_bounds__(kPar) void k_dm_r_fill(DM M) {
+__device__ __forceinline__ void dm_r_fill_body(const DM& M) {
     if (M.cnt[C_ABORT]) return;
     const int nnew = M.cnt[C_NNEW];
     for (int r = blockIdx.x * kPar + threadIdx.x; r < nnew; r += gridDim.x * kPar) {
@@ -881,7 +884,7 @@ __global__ __launch_bounds__(kPar) void k_dm_r_fill(DM M) {
     }
 }
 // (8) each parent's new children in creation order appended to its children set; index entries of the new voxels
-__global__ __launch_bounds__(kPar) void k_dm_r_append(DM M) {
+__device__ __forceinline__ void dm_r_append_body(const DM& M) {
     if (M.cnt[C_ABORT]) return;
     const int nnew = M.cnt[C_NNEW], n0 = M.cnt[C_N0], n1 = M.cnt[C_N1];
     for (int r = blockIdx.x * kPar + threadIdx.x; r < nnew; r += gridDim.x * kPar) {
@@ -905,7 +908,7 @@ __global__ __launch_bounds__(kPar) void k_dm_r_append(DM M) {
     }
 }
 // (9) the grouping hashes return to empty (only the slots this update used); the new counts
-__global__ __launch_bounds__(kPar) void k_dm_a_done(DM M, int n_host, const int* dn) {
+__device__ __forceinline__ void dm_a_done_body(const DM& M, int n_host, const int* dn) {
     const int n = npts(M, n_host, dn);
     const int ab = M.cnt[C_ABORT];
     const int nreg = ab == 1 ? 0 : M.cnt[C_NNEW];
@@ -962,7 +965,7 @@ __device__ void dm_touched_one(const DM& M, int t, float* cs) {
     M.plan[lp] = planarity;
     M.last[lp] = cnt;
 }
-__global__ __launch_bounds__(64) void k_dm_touched(DM M) {       // 64-lane workgroups: the fits spread over CUs
+__device__ __forceinline__ void dm_touched_body(const DM& M) {       // 64-lane workgroups: the fits spread over CUs
     __shared__ float s_cs[64 * 3 * kKids];                           // each lane's child centroids (not scratch)
     const int nt = M.cnt[C_NT];
     for (int t = blockIdx.x * 64 + threadIdx.x; t < nt; t += gridDim.x * 64)
@@ -971,7 +974,7 @@ __global__ __launch_bounds__(64) void k_dm_touched(DM M) {       // 64-lane work
 
 // planarity failures in touched order: the voxel's children (child order), then the voxel; then the table patch of
 // every changed key
-__global__ __launch_bounds__(kOrch) void k_dm_finish(DM M) {
+__device__ __forceinline__ void dm_finish_body(const DM& M) {
     unsigned long long st_t0 = M.st ? __builtin_amdgcn_s_memtime() : 0ull;
     __shared__ int s_w[64];
     __shared__ int s_sim[8 * kSimLds];
@@ -1030,7 +1033,7 @@ __global__ __launch_bounds__(kOrch) void k_dm_finish(DM M) {
 }
 
 // the ICP table: every changed key's final state (unregistered parents, touched voxels; erased ones are absent)
-__global__ __launch_bounds__(kPar) void k_dm_table(DM M) {
+__device__ __forceinline__ void dm_table_body(const DM& M) {
     const int nc = M.cnt[C_NCHG], nt = M.cnt[C_NT];
     for (int k = blockIdx.x * kPar + threadIdx.x; k < nc + nt; k += gridDim.x * kPar) {
         const uint64_t key = k < nc ? M.chg[k] : M.T[k - nc];
@@ -1040,12 +1043,12 @@ __global__ __launch_bounds__(kPar) void k_dm_table(DM M) {
                 &M.cnt[C_TTOMB]);
     }
 }
-__global__ void k_dm_table_check(DM M) {
+__device__ __forceinline__ void dm_table_check_body(const DM& M) {
     if (threadIdx.x == 0 && 4 * M.cnt[C_TTOMB] > (1 << M.tabl)) M.cnt[C_REBUILD] |= R_TAB;
 }
 
 // renewal of the tombstoned indices / table when flagged (clear pass, then insert pass)
-__global__ __launch_bounds__(kPar) void k_dm_rebuild_clear(DM M) {
+__device__ __forceinline__ void dm_rebuild_clear_body(const DM& M) {
     const int fl = M.cnt[C_REBUILD];
     if (!fl) return;
     const size_t stride = static_cast<size_t>(gridDim.x) * kPar;
@@ -1058,7 +1061,7 @@ __global__ __launch_bounds__(kPar) void k_dm_rebuild_clear(DM M) {
             for (int a = 0; a < 3; ++a) { M.tab[i].n[a] = 0.0f; M.tab[i].c[a] = 0.0f; }
         }
 }
-__global__ __launch_bounds__(kPar) void k_dm_rebuild_fill(DM M) {
+__device__ __forceinline__ void dm_rebuild_fill_body(const DM& M) {
     const int fl = M.cnt[C_REBUILD];
     if (!fl) return;
     const int stride = gridDim.x * kPar;
@@ -1074,6 +1077,74 @@ __global__ __launch_bounds__(kPar) void k_dm_rebuild_fill(DM M) {
         if (fl & R_TAB) M.cnt[C_TTOMB] = 0;
     }
 }
+
+// ---------------------------------------------------------------------------------------------- the update's kernels
+// Every phase above is a __device__ body on `const DM&`; k_dm_X runs it on one map (the descriptor in the kernel
+// arguments), k_dm_X_b on the maps of a batch: blockIdx.y = active slot, its job's descriptor read from the batch's
+// device array.  blockIdx.x / gridDim.x stay "the workgroups of this map" in both forms.
+struct DMJob {
+    DM M;
+    const float* scan;                   // the context's device-filtered scan and its device count
+    const int* scan_n;
+    float* d_in;                         // the map's world-point buffer
+};
+struct DmJobPrm { DmParams P; int job; int pad; };       // per active slot: this update's parameters and its job
+#define DM_JOB const DMJob* __restrict__ jobs, const DmJobPrm* __restrict__ prm
+#define DM_J const DMJob& J = jobs[prm[blockIdx.y].job]; const DM M = J.M
+
+__global__ __launch_bounds__(kPar) void k_dm_world(DM M, const float* in, const int* dn, float* out) { dm_world_body(M, in, dn, out); }
+__global__ __launch_bounds__(kPar) void k_dm_world_b(DM_JOB) { DM_J; dm_world_body(M, J.scan, J.scan_n, J.d_in); }
+__global__ void k_dm_setprm(DM M, DmParams P) { dm_setprm_body(M, P); }
+__global__ void k_dm_setprm_b(DM_JOB) { DM_J; dm_setprm_body(M, prm[blockIdx.y].P); }
+__global__ __launch_bounds__(kPar) void k_dm_prune_mark(DM M, const int* dn) { dm_prune_mark_body(M, dn); }
+__global__ __launch_bounds__(kPar) void k_dm_prune_mark_b(DM_JOB) { DM_J; dm_prune_mark_body(M, M.prm_n); }
+__global__ __launch_bounds__(kPar) void k_dm_prune_compact(DM M, const int* dn) { dm_prune_compact_body(M, dn); }
+__global__ __launch_bounds__(kPar) void k_dm_prune_compact_b(DM_JOB) { DM_J; dm_prune_compact_body(M, M.prm_n); }
+__global__ __launch_bounds__(kOrch) void k_dm_unregister(DM M) { dm_unregister_body(M); }
+__global__ __launch_bounds__(kOrch) void k_dm_unregister_b(DM_JOB) { DM_J; dm_unregister_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_keys(DM M, const float* pts, int n_host, const int* dn) { dm_keys_body(M, pts, n_host, dn); }
+__global__ __launch_bounds__(kPar) void k_dm_keys_b(DM_JOB) { DM_J; dm_keys_body(M, J.d_in, 0, M.prm_n); }
+__global__ __launch_bounds__(kPar) void k_dm_a_count(DM M, int n_host, const int* dn) { dm_a_count_body(M, n_host, dn); }
+__global__ __launch_bounds__(kPar) void k_dm_a_count_b(DM_JOB) { DM_J; dm_a_count_body(M, 0, M.prm_n); }
+__global__ __launch_bounds__(kOrch) void k_dm_scan3(DM M, int stage) { dm_scan3_body(M, stage); }
+__global__ __launch_bounds__(kOrch) void k_dm_scan3_b(DM_JOB, int stage) { DM_J; dm_scan3_body(M, stage); }
+__global__ __launch_bounds__(kPar) void k_dm_a_rank(DM M, int n_host, const int* dn) { dm_a_rank_body(M, n_host, dn); }
+__global__ __launch_bounds__(kPar) void k_dm_a_rank_b(DM_JOB) { DM_J; dm_a_rank_body(M, 0, M.prm_n); }
+__global__ __launch_bounds__(kPar) void k_dm_a_fill(DM M, int n_host, const int* dn) { dm_a_fill_body(M, n_host, dn); }
+__global__ __launch_bounds__(kPar) void k_dm_a_fill_b(DM_JOB) { DM_J; dm_a_fill_body(M, 0, M.prm_n); }
+__global__ __launch_bounds__(kPar) void k_dm_a_mean(DM M, const float* pts, int n_host, const int* dn) { dm_a_mean_body(M, pts, n_host, dn); }
+__global__ __launch_bounds__(kPar) void k_dm_a_mean_b(DM_JOB) { DM_J; dm_a_mean_body(M, J.d_in, 0, M.prm_n); }
+__global__ __launch_bounds__(kPar) void k_dm_r_group(DM M) { dm_r_group_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_r_group_b(DM_JOB) { DM_J; dm_r_group_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_r_count(DM M) { dm_r_count_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_r_count_b(DM_JOB) { DM_J; dm_r_count_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_r_rank(DM M) { dm_r_rank_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_r_rank_b(DM_JOB) { DM_J; dm_r_rank_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_r_fill(DM M) { dm_r_fill_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_r_fill_b(DM_JOB) { DM_J; dm_r_fill_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_r_append(DM M) { dm_r_append_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_r_append_b(DM_JOB) { DM_J; dm_r_append_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_a_done(DM M, int n_host, const int* dn) { dm_a_done_body(M, n_host, dn); }
+__global__ __launch_bounds__(kPar) void k_dm_a_done_b(DM_JOB) { DM_J; dm_a_done_body(M, 0, M.prm_n); }
+__global__ __launch_bounds__(64) void k_dm_touched(DM M) { dm_touched_body(M); }
+__global__ __launch_bounds__(64) void k_dm_touched_b(DM_JOB) { DM_J; dm_touched_body(M); }
+__global__ __launch_bounds__(kOrch) void k_dm_finish(DM M) { dm_finish_body(M); }
+__global__ __launch_bounds__(kOrch) void k_dm_finish_b(DM_JOB) { DM_J; dm_finish_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_table(DM M) { dm_table_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_table_b(DM_JOB) { DM_J; dm_table_body(M); }
+__global__ void k_dm_table_check(DM M) { dm_table_check_body(M); }
+__global__ void k_dm_table_check_b(DM_JOB) { DM_J; dm_table_check_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_rebuild_clear(DM M) { dm_rebuild_clear_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_rebuild_clear_b(DM_JOB) { DM_J; dm_rebuild_clear_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_rebuild_fill(DM M) { dm_rebuild_fill_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_rebuild_fill_b(DM_JOB) { DM_J; dm_rebuild_fill_body(M); }
+// the error bits of all maps of a batch, gathered for one copy (lo_batch_maps_status)
+__global__ __launch_bounds__(kPar) void k_dm_status_b(const DMJob* __restrict__ jobs, int count, int* __restrict__ out) {
+    const int j = blockIdx.x * kPar + threadIdx.x;
+    if (j < count) out[j] = jobs[j].M.cnt ? jobs[j].M.cnt[C_ERR] : 0;      // (a job without a map: cleared entry)
+}
+#undef DM_J
+#undef DM_JOB
 
 // ---------------------------------------------------------------------------------------------- ApplyTransformAndRehash
 // (:264-302) every L0 centroid moved (R c + t, Matrix3f * Vector3f) and re-keyed; the rebuilt L0 holds the keys in
@@ -1268,6 +1339,7 @@ struct lo_devmap {
     hipEvent_t ev_err = nullptr;         //   recorded after that copy
     bool err_pending = false;
     size_t updates = 0;
+    uint64_t uid = 0;                    // distinguishes maps in a batch's descriptor cache (an address may be reused)
 };
 
 template <class T>
@@ -1327,6 +1399,8 @@ lo_devmap* lo_devmap_create(lo_ctx* ctx, float voxel_size, int hierarchy_factor,
     // a KDTree-mode context reads the map's L0 centroids through its grid (lo_devmap_sync_points); the surfel table
     // the map keeps is then unused by its ICP
     lo_devmap* m = new lo_devmap();
+    static std::atomic<uint64_t> next_uid{1};
+    m->uid = next_uid.fetch_add(1, std::memory_order_relaxed);
     m->ctx = ctx;
     m->device = lo_device(ctx);
     m->stream = static_cast<hipStream_t>(lo_stream(ctx));
@@ -1647,6 +1721,269 @@ size_t lo_devmap_get_l1(lo_devmap* m, int32_t* keys, uint8_t* has_surfel, float*
                     children[(i * kKids + q) * 3 + a] = q < nk[i] ? unp(kids[i * kKids + q], a) : 0;
     }
     return n;
+}
+
+}  // extern "C"
+
+// ================================================================================================== maps of a batch
+// lo_batch_update_maps / lo_batch_maps_status (include/lo_map.h): the update pipeline above, one launch per phase for
+// all active jobs on the batch stream.  The batch keeps a device array of the jobs' descriptors (map, scan, point
+// buffer); entry j goes up again only when it changed -- another map, a moved or replaced table (dm_bind_table), other
+// scan buffers.  What changes per update (DmParams and the active list) goes up in one copy.
+namespace {
+
+struct BatchMaps {
+    int device = 0;
+    DevBuf<DMJob> d_jobs;
+    PinnedBuf<DMJob> h_jobs;             // what d_jobs holds (pinned: entries go up with stream-ordered copies)
+    std::vector<uint64_t> uid;           //   and whose map (0: nothing yet)
+    DevBuf<DmJobPrm> d_prm;
+    PinnedBuf<DmJobPrm> h_prm;
+    hipEvent_t ev_prm = nullptr;         // the last call's uploads have read h_jobs and h_prm
+    bool prm_pending = false;
+    hipEvent_t ev_tab = nullptr;         // a context stream's table refill, for the batch stream to wait on
+    hipEvent_t ev_done = nullptr;        // the last update's launches, waited for before such a refill (it clears or
+    bool done_recorded = false;          //   frees the table and reads the map the update may still write)
+    DevBuf<int> d_err;
+    PinnedBuf<int> h_err;
+};
+
+void bm_release(void* p) {
+    BatchMaps* S = static_cast<BatchMaps*>(p);
+    (void)hipSetDevice(S->device);
+    if (S->ev_prm) (void)hipEventDestroy(S->ev_prm);
+    if (S->ev_tab) (void)hipEventDestroy(S->ev_tab);
+    if (S->ev_done) (void)hipEventDestroy(S->ev_done);
+    delete S;
+}
+
+struct BatchErr { std::string err; };    // LO_HIP's handle; copied into the batch's error text on failure
+
+int bm_state(lo_batch* b, const BatchView& V, BatchMaps** out, BatchErr* e) {
+    void** slot = batch_map_state(b, bm_release);
+    if (!*slot) {
+        BatchMaps* S = new BatchMaps();
+        S->device = V.device;
+        *slot = S;                                           // owned by the batch from here on
+        const size_t B = static_cast<size_t>(V.count);
+        LO_HIP(e, S->d_jobs.reserve(B));
+        LO_HIP(e, S->d_prm.reserve(B));
+        LO_HIP(e, S->h_prm.reserve(B));
+        LO_HIP(e, S->d_err.reserve(B));
+        LO_HIP(e, S->h_err.reserve(B));
+        LO_HIP(e, hipEventCreateWithFlags(&S->ev_prm, hipEventDisableTiming));
+        LO_HIP(e, hipEventCreateWithFlags(&S->ev_tab, hipEventDisableTiming));
+        LO_HIP(e, hipEventCreateWithFlags(&S->ev_done, hipEventDisableTiming));
+        LO_HIP(e, S->h_jobs.reserve(B));
+        for (size_t j = 0; j < B; ++j) S->h_jobs[j] = DMJob{};
+        // (a job without a map: null pointers.  On the batch stream: a null-stream memset is not ordered before the
+        // entries' uploads there and could land on top of them)
+        LO_HIP(e, hipMemsetAsync(S->d_jobs, 0, sizeof(DMJob) * B, static_cast<hipStream_t>(V.stream)));
+        S->uid.assign(B, 0);
+    }
+    *out = static_cast<BatchMaps*>(*slot);
+    if ((*out)->uid.size() != static_cast<size_t>(V.count)) { e->err = "map state of the batch was not allocated"; return LO_ERR_HIP; }
+    if ((*out)->prm_pending) {                               // the previous call's uploads still read h_jobs / h_prm
+        LO_HIP(e, hipEventSynchronize((*out)->ev_prm));
+        (*out)->prm_pending = false;
+    }
+    return LO_OK;
+}
+
+// Entry j of the descriptor array brought up to date with maps[j] (null: cleared).  bind: the update's own preparation
+// -- the context's table bound and the context's filtered scan looked up; without it (status) only the map's own
+// buffers matter.  A replaced table is emptied (or freed and allocated anew) and refilled on the context stream: the
+// host first waits for the batch's last update (which may still patch the table and write the map), and the batch
+// stream then waits for the refill.  *uploaded is set when the entry went up (the caller records ev_prm behind the copies).
+int bm_refresh(const BatchView& V, BatchMaps* S, lo_devmap* m, int j, bool bind, bool* uploaded, BatchErr* e) {
+    hipStream_t bs = static_cast<hipStream_t>(V.stream);
+    DMJob& H = S->h_jobs[j];
+    if (!m) {
+        if (S->uid[j] == 0) return LO_OK;
+        H = DMJob{};
+        S->uid[j] = 0;
+        *uploaded = true;
+        LO_HIP(e, hipMemcpyAsync(S->d_jobs + j, &H, sizeof(DMJob), hipMemcpyHostToDevice, bs));
+        return LO_OK;
+    }
+    const float* scan = S->uid[j] == m->uid ? H.scan : nullptr;
+    const int* scan_n = S->uid[j] == m->uid ? H.scan_n : nullptr;
+    if (bind) {
+        dm_stream(m);
+        const uint64_t gen = m->tab_gen;
+        // (on the host: a table that has to grow is freed by ctx_reserve_table after it waited for the context
+        // stream only, and the batch's last update may still patch it on the batch stream.  Rare path.)
+        if (S->done_recorded && !ctx_table_current(m->ctx, size_t(4) * static_cast<size_t>(m->M.C1)))
+            LO_HIP(e, hipEventSynchronize(S->ev_done));
+        int rc = dm_bind_table(m);
+        if (rc != LO_OK) { e->err = m->err; return rc; }
+        if (m->tab_gen != gen) {
+            LO_HIP(e, hipEventRecord(S->ev_tab, m->stream));
+            LO_HIP(e, hipStreamWaitEvent(bs, S->ev_tab, 0));
+        }
+        rc = ctx_filtered_device(m->ctx, &scan, &scan_n);
+        if (rc != LO_OK) { e->err = lo_last_error(m->ctx); return rc; }
+    }
+    if (S->uid[j] == m->uid && H.M.tab == m->M.tab && H.M.tabl == m->M.tabl && H.scan == scan && H.scan_n == scan_n)
+        return LO_OK;
+    H.M = m->M;
+    H.scan = scan;
+    H.scan_n = scan_n;
+    H.d_in = m->d_in;
+    S->uid[j] = m->uid;
+    *uploaded = true;
+    LO_HIP(e, hipMemcpyAsync(S->d_jobs + j, &H, sizeof(DMJob), hipMemcpyHostToDevice, bs));
+    return LO_OK;
+}
+
+int bm_check_maps(const BatchView& V, lo_devmap* const* maps, const unsigned char* active, BatchErr* e) {
+    for (int j = 0; j < V.count; ++j) {
+        if (active && !active[j]) continue;
+        if (!active && !maps[j]) continue;                   // status: a job that has no map
+        if (!maps[j] || maps[j]->ctx != V.ctx[j]) {
+            e->err = "maps[" + std::to_string(j) + "] is not a map of the batch's context " + std::to_string(j);
+            return LO_ERR_ARG;
+        }
+    }
+    return LO_OK;
+}
+
+int bm_update(lo_batch* b, const BatchView& V, lo_devmap* const* maps, const unsigned char* active, const float* T,
+              double max_distance, BatchErr* e) {
+    if (V.pending) { e->err = "batch in flight: call lo_batch_result first"; return LO_ERR_STATE; }
+    int rc = bm_check_maps(V, maps, active, e);
+    if (rc != LO_OK) return rc;
+    LO_HIP(e, hipSetDevice(V.device));
+    BatchMaps* S = nullptr;
+    if ((rc = bm_state(b, V, &S, e)) != LO_OK) return rc;
+    hipStream_t bs = static_cast<hipStream_t>(V.stream);
+    int nact = 0;
+    bool up = false;
+    long long n_max = 1;
+    size_t c0_max = 1, slots_max = 1;
+    for (int j = 0; j < V.count; ++j) {
+        if (!active[j]) continue;
+        lo_devmap* m = maps[j];
+        if ((rc = bm_refresh(V, S, m, j, true, &up, e)) != LO_OK) {
+            if (up && hipEventRecord(S->ev_prm, bs) == hipSuccess) S->prm_pending = true;
+            return rc;
+        }
+        DmJobPrm& Q = S->h_prm[nact++];
+        const float* Tj = T + 12 * j;
+        Q = DmJobPrm{};
+        Q.P.v[0] = static_cast<float>(static_cast<double>(Tj[3]));       // the sensor position: Vector3f -> Vector3d
+        Q.P.v[1] = static_cast<float>(static_cast<double>(Tj[7]));       //   and back, as lo_devmap_update_from_scan
+        Q.P.v[2] = static_cast<float>(static_cast<double>(Tj[11]));
+        Q.P.v[3] = static_cast<float>(max_distance * max_distance);
+        std::memcpy(Q.P.v + 4, Tj, 12 * sizeof(float));
+        Q.P.n = 0;
+        Q.P.from_scan = 1;
+        Q.job = j;
+        const DM& M = m->M;
+        const long long known = ctx_filtered_count_known(m->ctx);
+        n_max = std::max(n_max, known >= 0 ? std::min<long long>(known, M.NP) : static_cast<long long>(M.NP));
+        c0_max = std::max(c0_max, static_cast<size_t>(M.C0));
+        slots_max = std::max({slots_max, size_t(1) << M.h0l, size_t(1) << M.h1l, size_t(1) << M.tabl});
+        ++m->updates;
+    }
+    if (nact == 0) return LO_OK;
+    LO_HIP(e, hipMemcpyAsync(S->d_prm, S->h_prm, sizeof(DmJobPrm) * nact, hipMemcpyHostToDevice, bs));
+    LO_HIP(e, hipEventRecord(S->ev_prm, bs));
+    S->prm_pending = true;
+    // grid.x: what the largest active job needs (the single map's launch sizes itself from its capacities); the
+    // ordered point passes keep their kChunk workgroups per map (k_dm_scan3 scans exactly that many counts)
+    const unsigned ny = static_cast<unsigned>(nact);
+    auto blocks = [](long long items, int per, int cap) {
+        return static_cast<unsigned>(std::max<long long>(1, std::min<long long>(cap, (items + per - 1) / per)));
+    };
+    const dim3 grid(blocks(n_max, kPar, 1024), ny), tgrid(blocks(n_max, 64, 1024), ny), chunks(kChunk, ny);
+    const dim3 pgrid(blocks(static_cast<long long>(c0_max), 4 * kPar, kPruneBlocks), ny);
+    const dim3 rgrid(std::min(blocks(static_cast<long long>(slots_max), 4 * kPar, 1024), std::max(1u, 65536u / ny)), ny);
+    const dim3 one(1, ny), par(kPar), orch(kOrch);
+    const DMJob* J = S->d_jobs;
+    const DmJobPrm* Q = S->d_prm;
+    hipLaunchKernelGGL(k_dm_setprm_b, one, dim3(64), 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_world_b, grid, par, 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_prune_mark_b, pgrid, par, 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_prune_compact_b, pgrid, par, 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_unregister_b, one, orch, 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_keys_b, grid, par, 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_a_count_b, chunks, par, 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_scan3_b, one, orch, 0, bs, J, Q, 1);
+    hipLaunchKernelGGL(k_dm_a_rank_b, chunks, par, 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_a_fill_b, grid, par, 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_a_mean_b, grid, par, 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_r_group_b, grid, par, 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_r_count_b, chunks, par, 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_scan3_b, one, orch, 0, bs, J, Q, 2);
+    hipLaunchKernelGGL(k_dm_r_rank_b, chunks, par, 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_r_fill_b, grid, par, 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_r_append_b, grid, par, 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_a_done_b, grid, par, 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_touched_b, tgrid, dim3(64), 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_finish_b, one, orch, 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_table_b, grid, par, 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_table_check_b, one, dim3(64), 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_rebuild_clear_b, rgrid, par, 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_rebuild_fill_b, rgrid, par, 0, bs, J, Q);
+    LO_HIP(e, hipGetLastError());
+    LO_HIP(e, hipEventRecord(S->ev_done, bs));
+    S->done_recorded = true;
+    return LO_OK;
+}
+
+int bm_status(lo_batch* b, const BatchView& V, lo_devmap* const* maps, int* out, BatchErr* e) {
+    int rc = bm_check_maps(V, maps, nullptr, e);
+    if (rc != LO_OK) return rc;
+    LO_HIP(e, hipSetDevice(V.device));
+    BatchMaps* S = nullptr;
+    if ((rc = bm_state(b, V, &S, e)) != LO_OK) return rc;
+    hipStream_t bs = static_cast<hipStream_t>(V.stream);
+    bool up = false;
+    for (int j = 0; j < V.count; ++j)
+        if ((rc = bm_refresh(V, S, maps[j], j, false, &up, e)) != LO_OK) break;
+    if (rc != LO_OK) {
+        (void)hipStreamSynchronize(bs);                      // (the copies enqueued so far have read h_jobs)
+        return rc;
+    }
+    hipLaunchKernelGGL(k_dm_status_b, dim3((V.count + kPar - 1) / kPar), dim3(kPar), 0, bs, S->d_jobs.get(), V.count,
+                       S->d_err.get());
+    LO_HIP(e, hipGetLastError());
+    LO_HIP(e, hipMemcpyAsync(S->h_err, S->d_err, sizeof(int) * V.count, hipMemcpyDeviceToHost, bs));
+    LO_HIP(e, hipStreamSynchronize(bs));
+    rc = LO_OK;
+    for (int j = 0; j < V.count; ++j) {
+        const int bits = maps[j] ? S->h_err[j] : 0;          // a job without a map reports LO_OK
+        if (out) out[j] = bits ? LO_ERR_CAPACITY : LO_OK;
+        if (!bits) continue;
+        maps[j]->err = "device map overflow / invalid key (error bits " + std::to_string(bits) + ")";
+        if (rc == LO_OK) e->err = "job " + std::to_string(j) + ": " + maps[j]->err;
+        rc = LO_ERR_CAPACITY;
+    }
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lo_batch_update_maps(lo_batch* b, lo_devmap* const* maps, const unsigned char* active, const float* T,
+                         double max_distance) {
+    if (!b) return LO_ERR_ARG;
+    if (!maps || !active || !T) { batch_set_error(b, "null argument"); return LO_ERR_ARG; }
+    BatchErr e;
+    const int rc = bm_update(b, batch_view(b), maps, active, T, max_distance, &e);
+    if (rc != LO_OK) batch_set_error(b, e.err.c_str());
+    return rc;
+}
+
+int lo_batch_maps_status(lo_batch* b, lo_devmap* const* maps, int* rc_out) {
+    if (!b) return LO_ERR_ARG;
+    if (!maps) { batch_set_error(b, "null argument"); return LO_ERR_ARG; }
+    BatchErr e;
+    const int rc = bm_status(b, batch_view(b), maps, rc_out, &e);
+    if (rc != LO_OK) batch_set_error(b, e.err.c_str());
+    return rc;
 }
 
 }  // extern "C"

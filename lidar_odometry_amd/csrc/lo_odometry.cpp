@@ -449,3 +449,221 @@ size_t lo_odom_map_surfels(const lo_odometry* o) {
 }
 
 }  // extern "C"
+
+// ================================================================================================== B sequences
+// lo_odom_batch_*: lo_odom_process for `count` sequences in lockstep (surfel mode, no loop closure), joined from the
+// batch's pieces: one batched filter, one batched optimize and one batched map update per call, and per job the same
+// lo::FrameState bookkeeping on the same values -- so job j's poses, keyframes, iterations and guesses are those of a
+// lo_odometry fed sequence j alone.
+struct lo_odom_batch {
+    lo_odom_config cfg{};
+    int count = 0;
+    std::vector<lo_ctx*> ctx;
+    lo_batch* batch = nullptr;
+    std::vector<lo_devmap*> maps;
+    std::vector<lo::FrameState> fs;
+    std::vector<SE3f> initial, pose;
+    std::vector<size_t> keyframes;
+    bool initialized = false;
+    bool status_due = false;              // keyframes were enqueued whose error bits nobody has read yet
+    std::string err;
+    std::vector<size_t> nf, counts;
+    std::vector<float> guess12, kf12;
+    std::vector<lo_batch_rec> recs;
+    std::vector<unsigned char> active, early;
+};
+
+static thread_local std::string g_odom_batch_create_err;   // why the calling thread's last create failed
+
+// create_keyframe for the jobs flagged in o->active at o->pose: one batched map update, then each job's pose part
+static int batch_keyframes(lo_odom_batch* o, lo_odom_frame* info) {
+    bool any = false;
+    for (int j = 0; j < o->count; ++j) {
+        if (!o->active[j]) continue;
+        any = true;
+        lo::se3_to12(o->pose[j], o->kf12.data() + 12 * j);
+    }
+    if (!any) return LO_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = lo_batch_update_maps(o->batch, o->maps.data(), o->active.data(), o->kf12.data(), o->cfg.max_range * 1.2);
+    if (rc != LO_OK) { o->err = std::string("keyframe map update: ") + lo_batch_last_error(o->batch); return rc; }
+    const double ms = ms_since(t0);
+    o->status_due = true;
+    for (int j = 0; j < o->count; ++j) {
+        if (!o->active[j]) continue;
+        ++o->keyframes[j];
+        if (info) { info[j].keyframe = 1; info[j].map_ms = ms; }
+        o->fs[j].on_keyframe(o->pose[j], nullptr);
+    }
+    return LO_OK;
+}
+
+// the error bits of the keyframes enqueued by the previous call(s), all jobs in one copy
+static int batch_map_status(lo_odom_batch* o) {
+    if (!o->status_due) return LO_OK;
+    o->status_due = false;
+    const int rc = lo_batch_maps_status(o->batch, o->maps.data(), nullptr);
+    if (rc != LO_OK) o->err = std::string("device map: ") + lo_batch_last_error(o->batch);
+    return rc;
+}
+
+extern "C" {
+
+lo_odom_batch* lo_odom_batch_create(const lo_odom_config* cfg, int count, int device, size_t max_l0, int* err) {
+    auto fail = [&](int rc, const std::string& msg, lo_odom_batch* o) -> lo_odom_batch* {
+        g_odom_batch_create_err = msg;
+        std::fprintf(stderr, "lo_odom_batch_create: %s\n", msg.c_str());
+        lo_odom_batch_destroy(o);
+        if (err) *err = rc;
+        return nullptr;
+    };
+    if (!cfg || count < 1 || count > 65535 || cfg->point_stride < 1 || !(cfg->filter_voxel_size > 0.0f))
+        return fail(LO_ERR_ARG, "need a config, 1..65535 sequences, point_stride >= 1 and filter_voxel_size > 0", nullptr);
+    if (!cfg->icp.use_surfel_correspondence)
+        return fail(LO_ERR_ARG, "KDTree-mode config: the batched frame loop is surfel mode only (the per-context "
+                                "lo_devmap_sync_points has no batched form)", nullptr);
+    lo_odom_batch* o = new (std::nothrow) lo_odom_batch();
+    if (!o) return fail(LO_ERR_ARG, "allocation", nullptr);
+    o->cfg = *cfg;
+    o->count = count;
+    for (int j = 0; j < count; ++j) {
+        int e = LO_OK;
+        lo_ctx* c = lo_create(&cfg->icp, device, &e);
+        if (!c) return fail(e, "lo_create failed for sequence " + std::to_string(j), o);
+        o->ctx.push_back(c);
+        lo_devmap* m = lo_devmap_create(c, cfg->icp.voxel_size, cfg->icp.hierarchy_factor, cfg->planarity_threshold, max_l0,
+                                        static_cast<size_t>(std::max(cfg->icp.max_points, 16)), &e);
+        if (!m) return fail(e, "lo_devmap_create failed for sequence " + std::to_string(j), o);
+        o->maps.push_back(m);
+    }
+    int e = LO_OK;
+    o->batch = lo_batch_create(o->ctx.data(), count, &e);
+    if (!o->batch) return fail(e, "lo_batch_create failed", o);
+    const size_t B = static_cast<size_t>(count);
+    o->fs.resize(B);
+    o->initial.resize(B);
+    o->pose.resize(B);
+    o->keyframes.assign(B, 0);
+    o->nf.assign(B, 0);
+    o->counts.assign(B, 0);
+    o->guess12.assign(12 * B, 0.0f);
+    o->kf12.assign(12 * B, 0.0f);
+    o->recs.resize(B);
+    o->active.assign(B, 0);
+    o->early.assign(B, 0);
+    if (err) *err = LO_OK;
+    return o;
+}
+
+void lo_odom_batch_destroy(lo_odom_batch* o) {
+    if (!o) return;
+    lo_batch_destroy(o->batch);                          // (waits for the batch stream, where the map updates run)
+    for (lo_devmap* m : o->maps) lo_devmap_destroy(m);
+    for (lo_ctx* c : o->ctx) lo_destroy(c);
+    delete o;
+}
+
+const char* lo_odom_batch_last_error(const lo_odom_batch* o) { return o ? o->err.c_str() : g_odom_batch_create_err.c_str(); }
+
+int lo_odom_batch_set_initial_pose(lo_odom_batch* o, int job, const float T[12]) {
+    if (!o || !T || job < 0 || job >= o->count) return LO_ERR_ARG;
+    o->initial[job] = lo::se3_from12(T);
+    return LO_OK;
+}
+
+int lo_odom_batch_set_exact(lo_odom_batch* o, int enable) {
+    if (!o) return LO_ERR_ARG;
+    for (lo_ctx* c : o->ctx) {
+        const int rc = lo_set_exact(c, enable);
+        if (rc != LO_OK) { o->err = lo_last_error(c); return rc; }
+    }
+    return LO_OK;
+}
+
+int lo_odom_batch_process(lo_odom_batch* o, const float* const* raw, const size_t* n, float* T_out, lo_odom_frame* info) {
+    if (!o) return LO_ERR_ARG;
+    if (!raw || !n || !T_out) { o->err = "null argument"; return LO_ERR_ARG; }
+    const int B = o->count;
+    if (info) std::memset(info, 0, sizeof(lo_odom_frame) * B);
+    // preprocess_frame for every sequence (an early-return sequence's scan is filtered too: its count is not reported)
+    int rc = lo_batch_filter_raw_host(o->batch, raw, n, o->cfg.point_stride, o->cfg.filter_voxel_size, o->nf.data());
+    if (rc != LO_OK) { o->err = lo_batch_last_error(o->batch); return rc; }
+    if (!o->initialized) {                                                    // initialize_first_frame (:235-269)
+        for (int j = 0; j < B; ++j) {
+            o->fs[j].init(o->initial[j]);
+            o->pose[j] = o->initial[j];
+            o->active[j] = o->nf[j] > 0 ? 1 : 0;
+            lo::se3_to12(o->initial[j], T_out + 12 * j);
+            if (info) {
+                info[j].n_filtered = static_cast<int>(o->nf[j]);
+                lo::se3_to12(o->initial[j], info[j].guess);
+                info[j].status = LO_OK;
+            }
+        }
+        rc = batch_keyframes(o, info);
+        if (rc != LO_OK) return rc;
+        o->initialized = true;
+        return LO_OK;
+    }
+    std::vector<SE3f>& guess = o->pose;                   // the guesses until the commit, the poses after it
+    for (int j = 0; j < B; ++j) {
+        o->early[j] = o->keyframes[j] == 0 ? 1 : 0;
+        o->counts[j] = 0;
+        if (o->early[j]) {                                // "No keyframe available" (Estimator.cpp:140-144)
+            lo::se3_to12(o->fs[j].prev_pose(), o->guess12.data() + 12 * j);
+            continue;
+        }
+        guess[j] = o->fs[j].guess();                      // :154
+        if (info) lo::se3_to12(guess[j], info[j].guess);
+        SE3f g_in = guess[j];
+        lo::so3_project_svd(guess[j].R, g_in.R);          // :284
+        lo::se3_to12(g_in, o->guess12.data() + 12 * j);
+        o->counts[j] = o->nf[j];
+    }
+    rc = lo_batch_optimize_async(o->batch, nullptr, o->counts.data(), o->guess12.data());
+    if (rc != LO_OK) { o->err = lo_batch_last_error(o->batch); return rc; }
+    double ms = 0.0;
+    rc = lo_batch_result(o->batch, o->recs.data(), &ms);
+    if (rc != LO_OK) { o->err = lo_batch_last_error(o->batch); return rc; }
+    // the last keyframes' map updates ran before this frame's ICP on the same stream: their error bits, once per call
+    if ((rc = batch_map_status(o)) != LO_OK) return rc;
+    for (int j = 0; j < B; ++j) {
+        o->active[j] = 0;
+        float* To = T_out + 12 * j;
+        if (o->early[j]) {
+            std::memcpy(To, o->guess12.data() + 12 * j, 12 * sizeof(float));
+            if (info) { std::memcpy(info[j].guess, To, sizeof(info[j].guess)); info[j].status = LO_OK; }
+            continue;
+        }
+        const lo_batch_rec& R = o->recs[j];
+        if (info) {
+            info[j].status = R.status;
+            info[j].icp_iterations = R.iterations;
+            info[j].n_corr = R.n_corr;
+            info[j].device_ms = ms;
+            info[j].n_filtered = static_cast<int>(o->nf[j]);
+        }
+        SE3f pose = guess[j];                             // a failed job keeps the guess (:304-307)
+        if (R.status == LO_OK) {
+            const SE3f r = lo::se3_from12(R.pose);
+            pose = r;
+            lo::so3_project_svd(r.R, pose.R);             // :308
+        }
+        lo::se3_to12(pose, To);
+        o->pose[j] = pose;
+        o->active[j] = o->fs[j].commit(pose, o->cfg.keyframe_distance, o->cfg.keyframe_rotation) ? 1 : 0;
+    }
+    return batch_keyframes(o, info);
+}
+
+int lo_odom_batch_flush(lo_odom_batch* o) {
+    if (!o) return LO_ERR_ARG;
+    o->status_due = true;                                 // synchronous: the last updates' error bits, read or not
+    return batch_map_status(o);
+}
+
+size_t lo_odom_batch_keyframe_count(const lo_odom_batch* o, int job) {
+    return (o && job >= 0 && job < o->count) ? o->keyframes[job] : 0;
+}
+
+}  // extern "C"

@@ -104,6 +104,14 @@ int ctx_filtered_device(lo_ctx* c, const float** d_pts, const int** d_n) {
     return LO_OK;
 }
 
+bool ctx_table_current(const lo_ctx* c, size_t min_slots) {
+    return c && c->devmap_gen == c->tab_gen && c->devmap_gen != 0 && (size_t(1) << c->log2cap) >= min_slots;
+}
+
+long long ctx_filtered_count_known(const lo_ctx* c) {
+    return (c && c->last_dev_count && c->nf_valid && !c->pending) ? static_cast<long long>(*c->h_nf) : -1;
+}
+
 // a pinned staging buffer and its device copy, grown together (both freed before either is allocated)
 static int grow_pinned_pair(lo_ctx* c, PinnedBuf<void>& h, DevBuf<void>& d, size_t bytes) {
     if (bytes <= std::min(h.capacity(), d.capacity())) return LO_OK;

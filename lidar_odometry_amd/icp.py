@@ -536,3 +536,35 @@ class BatchOptimizer:
         self._check(lib().lo_batch_result(self._b, recs, C.byref(ms)))
         self.last_gpu_ms = ms.value
         return self._results(recs)
+
+    def _map_handles(self, maps):
+        B = len(self.optimizers)
+        if len(maps) != B:
+            raise ValueError(f"need {B} maps (None for a job that is never active)")
+        return (C.c_void_p * B)(*[m._h if m is not None else None for m in maps])
+
+    def update_maps(self, maps, active, poses, max_distance: float):
+        """The keyframes' UpdateVoxelMap for all active jobs in one set of launches (lo_batch_update_maps): for each
+        job j with ``active[j]``, what ``lo_devmap_update_from_scan(maps[j], poses[j], max_distance)`` does -- the
+        context's filtered scan (``filter_raw``) moved to the world frame by the pose and inserted into the job's
+        ``DeviceVoxelMap``.  Enqueues on the batch stream and returns; ``maps_status`` waits."""
+        B = len(self.optimizers)
+        act = np.ascontiguousarray(np.asarray(active).astype(bool).astype(np.uint8))
+        if act.shape != (B,):
+            raise ValueError(f"need {B} active flags")
+        T = np.ascontiguousarray(np.stack([_as_pose(t) for t in poses]), dtype=np.float32)
+        if T.shape != (B, 12):
+            raise ValueError(f"need {B} poses")
+        self._check(lib().lo_batch_update_maps(self._b, self._map_handles(maps),
+                                               act.ctypes.data_as(C.POINTER(C.c_uint8)), _fptr(T),
+                                               float(max_distance)))
+
+    def maps_status(self, maps):
+        """Waits for the batch stream and returns every job's map status in one copy (lo_batch_maps_status):
+        ``LO_OK`` or ``LO_ERR_CAPACITY`` per job (an update that overflowed a capacity aborted)."""
+        B = len(self.optimizers)
+        rc = (C.c_int * B)()
+        r = lib().lo_batch_maps_status(self._b, self._map_handles(maps), rc)
+        if r < 0 and r != _lib.LO_ERR_CAPACITY:
+            self._check(r)
+        return [int(x) for x in rc]

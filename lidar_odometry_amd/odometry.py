@@ -194,4 +194,80 @@ class LidarOdometry:
         return int(lib().lo_odom_map_surfels(self._o))
 
 
-__all__ = ["LidarOdometry", "FrameInfo", "LoopConfig", "LoopEvent", "_lib"]
+class BatchLidarOdometry:
+    """B sensor streams on one GPU in lockstep (lo_odom_batch_*): ``process(raws)`` takes one raw scan per sequence
+    and returns one 3x4 world pose and one FrameInfo per sequence.  Each sequence's poses, keyframes, iteration counts
+    and guesses equal a ``LidarOdometry`` fed that sequence alone with the same settings.  Surfel mode only
+    (``use_surfel_correspondence=False`` raises), no loop closure.  ``max_l0``: every sequence's device-map capacity."""
+
+    def __init__(self, count: int, device: int = 0, max_points: int = 1 << 17, use_surfel_correspondence: bool = True,
+                 point_stride: int = 8, voxel_size: float = 0.5, map_voxel_size: float = 0.5, max_range: float = 100.0,
+                 keyframe_distance: float = 1.0, keyframe_rotation: float = 0.3, initial_poses=None,
+                 exact: bool = True, max_l0: int = 1 << 21):
+        cfg = LoOdomConfig()
+        lib().lo_odom_config_default_kitti(C.byref(cfg))
+        cfg.icp.max_points = int(max_points)
+        cfg.icp.use_surfel_correspondence = int(bool(use_surfel_correspondence))
+        cfg.icp.voxel_size = float(map_voxel_size)
+        cfg.point_stride = int(point_stride)
+        cfg.filter_voxel_size = float(voxel_size)
+        cfg.max_range = float(max_range)
+        cfg.keyframe_distance = float(keyframe_distance)
+        cfg.keyframe_rotation = float(keyframe_rotation)
+        err = C.c_int(0)
+        self._L = lib()
+        self.count = int(count)
+        self._o = self._L.lo_odom_batch_create(C.byref(cfg), self.count, int(device), int(max_l0), C.byref(err))
+        if not self._o:
+            why = self._L.lo_odom_batch_last_error(None).decode()
+            if err.value == _lib.LO_ERR_ARG:
+                raise ValueError(f"lo_odom_batch_create: {why} (code {err.value})")
+            raise RuntimeError(f"lo_odom_batch_create failed (code {err.value}): {why}")
+        if initial_poses is not None:
+            for j, P in enumerate(initial_poses):
+                if P is None:
+                    continue
+                T = np.ascontiguousarray(np.asarray(P, np.float32)[:3, :4].reshape(12))
+                self._checked(self._L.lo_odom_batch_set_initial_pose(self._o, j, T.ctypes.data_as(C.POINTER(C.c_float))))
+        self._checked(self._L.lo_odom_batch_set_exact(self._o, 1 if exact else 0))
+
+    def close(self):
+        h = getattr(self, "_o", None)
+        if h:
+            self._o = None
+            self._L.lo_odom_batch_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _checked(self, rc):
+        if rc < 0:
+            raise RuntimeError(f"lo_odom_batch error {rc}: {self._L.lo_odom_batch_last_error(self._o).decode()}")
+        return rc
+
+    def process(self, raws):
+        """One raw scan per sequence -> (poses (B, 3, 4) float32, [FrameInfo] * B)."""
+        B = self.count
+        pts = [np.ascontiguousarray(r, dtype=np.float32).reshape(-1, 3) for r in raws]
+        if len(pts) != B:
+            raise ValueError(f"need {B} raw scans")
+        ptrs = (C.c_void_p * B)(*[p.ctypes.data if len(p) else None for p in pts])
+        ns = (C.c_size_t * B)(*[len(p) for p in pts])
+        T = np.zeros((B, 12), np.float32)
+        info = (LoOdomFrame * B)()
+        self._checked(self._L.lo_odom_batch_process(self._o, ptrs, ns, T.ctypes.data_as(C.POINTER(C.c_float)), info))
+        return T.reshape(B, 3, 4), [FrameInfo(f.status, bool(f.keyframe), f.icp_iterations, f.n_filtered, f.n_corr,
+                                              f.device_ms, f.map_ms, f.guess) for f in info]
+
+    def flush(self):
+        """Wait for the last keyframes' map updates; raise if one overflowed its device map (lo_odom_batch_flush)."""
+        self._checked(self._L.lo_odom_batch_flush(self._o))
+
+    def keyframes(self, job: int) -> int:
+        return int(self._L.lo_odom_batch_keyframe_count(self._o, int(job)))
+
+
+__all__ = ["LidarOdometry", "BatchLidarOdometry", "FrameInfo", "LoopConfig", "LoopEvent", "_lib"]
