@@ -251,8 +251,10 @@ int lo_bench_correspond_rr(lo_ctx* const* ctxs, const float* const* d_pts, const
  * export, bit-identical to its lo_icp_optimize.  The batch runs on its own stream; the contexts must be idle while
  * it runs and each context's lo_icp_result() is not valid for a batched scan (use lo_batch_result).
  * The sequences' maps follow their keyframes through lo_batch_update_maps / lo_batch_maps_status (lo_map.h: the device
- * maps' update for all active jobs in one set of launches on the batch stream), and lo_odom_batch_* (lo_odometry.h)
- * is the whole frame loop for B sequences built on these entry points. */
+ * maps' update for all active jobs in one set of launches on the batch stream); a KDTree batch's grids follow the maps
+ * through lo_batch_sync_points (lo_map.h: lo_devmap_sync_points for all active jobs in one set of launches), and
+ * lo_odom_batch_* (lo_odometry.h) is the whole frame loop for B sequences, in either mode, built on these entry
+ * points. */
 typedef struct lo_batch lo_batch;
 typedef struct lo_batch_rec {
     float  pose[12];       /* optimized pose (T_init when status != LO_OK, as lo_icp_optimize) */
@@ -399,6 +401,13 @@ int lo_debug_counters_ex(lo_ctx* ctx, unsigned long long* out, int n);
 /* Diagnostic: bytes of device and pinned memory the library's handles (contexts, batches, device maps, loop detectors,
  * map builders) hold right now, process-wide.  Back at its earlier value once the handles made since are destroyed. */
 long long lo_debug_live_bytes(void);
+/* Diagnostic (tests): a KDTree-mode context's correspondence grid as it is now -- cell edge, origin and dimensions in
+ * cells, point count m, the dim[0] * dim[1] * dim[2] + 1 words of the cell starts and the m points as float4 (x, y, z,
+ * index bits).  Waits for the context's streams and for the device (a batch stream may have built the grid).  start
+ * and pts4 are nullable: a first call returns the sizes only.  LO_ERR_STATE on a surfel-mode context, LO_ERR_CAPACITY
+ * when start_cap (words) or pts_cap (points) is too small.  An all-pairs grid has no cells: no start words. */
+int lo_debug_grid(lo_ctx* ctx, float* h, int org[3], int dim[3], int* m, uint32_t* start, size_t start_cap, float* pts4,
+                  size_t pts_cap);
 /* Context-free host variant (no GPU needed): sample_size = gmm_sample_size. */
 int lo_pko_sample_indices_host(size_t n, int sample_size, int32_t* out);
 

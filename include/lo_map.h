@@ -140,6 +140,23 @@ int         lo_batch_update_maps(lo_batch* b, lo_devmap* const* maps, const unsi
  * such job, and each such map's lo_devmap_last_error is set).  maps[j] may be NULL for a job that has no map: it
  * reports LO_OK. */
 int         lo_batch_maps_status(lo_batch* b, lo_devmap* const* maps, int* rc);
+/* RebuildKdTree for the keyframes of a KDTree batch (every context use_surfel_correspondence = 0): for every job j with
+ * active[j] != 0, what lo_devmap_sync_points(maps[j]) does -- context j's correspondence grid rebuilt from map j's L0
+ * centroids in L0 order -- for all active jobs together on the batch stream, behind a preceding lo_batch_update_maps.
+ * Per call, whatever the number of jobs: eight launches (blockIdx.y = active job: the bounds, the clear of the cell
+ * counts, the cells and counts, a three-launch exclusive scan into the cell starts, the slot claim and the placement
+ * by in-cell rank -- no per-job sort), two host-to-device copies (the jobs' point arrays, then the grids' descriptors)
+ * and one device-to-host copy of seven words per job (the six bounds and the raw device count) with the call's one
+ * synchronise of the batch stream; the host sizes every grid from them and grows the contexts' buffers.  Context j
+ * afterwards holds what the single call gives on an identical map, bit for bit: geometry, point count, cell starts and
+ * points (sorted by cell, x fastest, index order inside a cell), no kd visit order, and the next optimize -- single or
+ * batched -- searches the new grid.  Distance ties re-run as after the single call (lo_kd_reruns).  The grids are
+ * built on the batch stream: before a context is used on its own (lo_icp_optimize, lo_knn_search), wait for it --
+ * lo_batch_maps_status does.  LO_ERR_STATE on a surfel-mode batch and while a batch optimize is in flight; LO_ERR_ARG
+ * when maps[j] of an active job was not created on context j; LO_ERR_CAPACITY when a job's raw count exceeds its
+ * array (lo_batch_last_error names the first such job; its grid is left as it was and the other jobs' grids are still
+ * built).  An inactive job's entry, grid and context are not touched. */
+int         lo_batch_sync_points(lo_batch* b, lo_devmap* const* maps, const unsigned char* active);
 
 #ifdef __cplusplus
 }

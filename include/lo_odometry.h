@@ -77,6 +77,7 @@ int           lo_odom_process(lo_odometry* o, const float* raw_xyz, size_t n, fl
 int           lo_odom_flush(lo_odometry* o);
 size_t        lo_odom_keyframe_count(const lo_odometry* o);
 size_t        lo_odom_map_surfels(const lo_odometry* o);
+int           lo_odom_kd_reruns(const lo_odometry* o);   /* lo_kd_reruns of the loop's context (KDTree mode) */
 
 /* ---- loop closure in the frame loop (opt-in) ----
  * The reference's SLAM back end around the frame loop: create_keyframe's loop bookkeeping (Estimator.cpp:370-530),
@@ -168,11 +169,17 @@ int       lo_odom_save_map_ply(lo_odometry* o, const char* path, float voxel_siz
  * and mode.  The maps' error bits are read once per call for all sequences, after the next call's ICP result (an
  * aborted update is reported -- LO_ERR_CAPACITY, the call returns before the poses are committed -- at the first call
  * after its keyframe); lo_odom_batch_flush reads them at once.
- * Surfel mode only: a KDTree config (use_surfel_correspondence = 0) is refused with LO_ERR_ARG (its per-context
- * lo_devmap_sync_points has no batched form); lo_odom_batch_last_error(NULL) says why the calling thread's last create failed.  No loop
- * closure.  info[j].device_ms is the whole batch's optimize; info[j].map_ms the batched update's enqueue. */
+ * lo_odom_batch_create is surfel mode only: a KDTree config (use_surfel_correspondence = 0) is refused with LO_ERR_ARG
+ * and belongs to lo_odom_batch_create_kdtree, which in turn refuses a surfel config with LO_ERR_ARG and is otherwise
+ * the same constructor: everything after creation is this one set of calls.  A KDTree loop rebuilds the grids of the
+ * sequences that made a keyframe with one lo_batch_sync_points (lo_map.h) directly after their lo_batch_update_maps
+ * (RebuildKdTree, Estimator.cpp:460-462), and equals a solo KDTree lo_odometry in the same fields and in lo_kd_reruns.
+ * lo_odom_batch_last_error(NULL) says why the calling thread's last create failed.  No loop closure.
+ * info[j].device_ms is the whole batch's optimize; info[j].map_ms the batched update's enqueue (KDTree: and the grid
+ * build with its synchronise). */
 typedef struct lo_odom_batch lo_odom_batch;
 lo_odom_batch* lo_odom_batch_create(const lo_odom_config* cfg, int count, int device, size_t max_l0, int* err);
+lo_odom_batch* lo_odom_batch_create_kdtree(const lo_odom_config* cfg, int count, int device, size_t max_l0, int* err);
 void        lo_odom_batch_destroy(lo_odom_batch* o);
 const char* lo_odom_batch_last_error(const lo_odom_batch* o);
 int lo_odom_batch_set_initial_pose(lo_odom_batch* o, int job, const float T[12]);
@@ -183,6 +190,7 @@ int lo_odom_batch_set_exact(lo_odom_batch* o, int enable);
 int lo_odom_batch_process(lo_odom_batch* o, const float* const* raw, const size_t* n, float* T_out, lo_odom_frame* info);
 int lo_odom_batch_flush(lo_odom_batch* o);     /* lo_batch_maps_status of the last keyframes */
 size_t lo_odom_batch_keyframe_count(const lo_odom_batch* o, int job);
+int lo_odom_batch_kd_reruns(const lo_odom_batch* o, int job);   /* lo_kd_reruns of sequence job's context */
 
 #ifdef __cplusplus
 }

@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = (
     "lo_map_point_count", "lo_icp_optimize", "lo_icp_optimize_raw_async", "lo_icp_optimize_raw", "lo_filtered_points",
     "lo_voxel_filter_gpu", "lo_icp_optimize_async", "lo_icp_optimize_loop", "lo_icp_optimize_loop_dev", "lo_loop_reruns", "lo_host_alloc", "lo_host_free",
     "lo_icp_result", "lo_sync", "lo_stream", "lo_set_stream", "lo_set_exact", "lo_set_pipeline", "lo_pipeline_status", "lo_set_pko_groups", "lo_update_config", "lo_map_sync_surfels", "lo_set_stage_timing", "lo_stage_time", "lo_pko_em_stats", "lo_icp_export_pose", "lo_bench_kernel", "lo_bench_correspond_rr", "lo_find_correspondences", "lo_knn_search", "lo_pko_scale_factor",
-    "lo_build_normal_equations", "lo_pko_sample_indices", "lo_pko_sample_indices_host", "lo_debug_counters", "lo_debug_counters_ex", "lo_debug_live_bytes", "lo_stage_span", "lo_seq_sum_f64", "lo_seq_sum_f32",
+    "lo_build_normal_equations", "lo_pko_sample_indices", "lo_pko_sample_indices_host", "lo_debug_counters", "lo_debug_counters_ex", "lo_debug_live_bytes", "lo_debug_grid", "lo_stage_span", "lo_seq_sum_f64", "lo_seq_sum_f32",
     "lo_batch_create", "lo_batch_destroy", "lo_batch_last_error", "lo_batch_size", "lo_batch_optimize_async",
     "lo_batch_result", "lo_batch_optimize", "lo_batch_bench_correspond",
     "lo_batch_filter_raw", "lo_batch_filter_raw_host", "lo_batch_filter_ms", "lo_batch_optimize_raw",
@@ -40,14 +40,15 @@ EXPORTED_SYMBOLS = (
     "lo_map_set_from_voxelmap", "lo_map_sync_voxelmap", "lo_voxelmap_apply_transform", "lo_map_patch_surfels", "lo_voxel_filter",
     "lo_voxelmap_set_device_fit", "lo_devmap_create", "lo_devmap_destroy", "lo_devmap_last_error", "lo_devmap_update",
     "lo_devmap_update_from_scan", "lo_devmap_apply_transform", "lo_devmap_counts", "lo_devmap_status", "lo_devmap_status_async", "lo_devmap_status_poll", "lo_devmap_sync_points", "lo_kd_reruns", "lo_devmap_get_l0", "lo_devmap_get_l1",
-    "lo_batch_update_maps", "lo_batch_maps_status",
+    "lo_batch_update_maps", "lo_batch_maps_status", "lo_batch_sync_points",
     # include/lo_odometry.h
     "lo_odom_config_default_kitti", "lo_odom_create", "lo_odom_destroy", "lo_odom_last_error", "lo_odom_set_initial_pose",
-    "lo_odom_process", "lo_odom_keyframe_count", "lo_odom_map_surfels", "lo_odom_set_exact", "lo_odom_flush",
+    "lo_odom_process", "lo_odom_keyframe_count", "lo_odom_map_surfels", "lo_odom_kd_reruns", "lo_odom_set_exact", "lo_odom_flush",
     "lo_loop_config_default", "lo_odom_enable_loop_closure", "lo_odom_last_loop", "lo_odom_loop_count",
     "lo_odom_keyframe_poses", "lo_odom_build_map", "lo_odom_map_points", "lo_odom_save_map_ply",
     "lo_odom_batch_create", "lo_odom_batch_destroy", "lo_odom_batch_last_error", "lo_odom_batch_set_initial_pose",
     "lo_odom_batch_set_exact", "lo_odom_batch_process", "lo_odom_batch_flush", "lo_odom_batch_keyframe_count",
+    "lo_odom_batch_create_kdtree", "lo_odom_batch_kd_reruns",
     # include/lo_io.h
     "lo_load_kitti_bin", "lo_load_ply", "lo_kitti_pose_line", "lo_save_trajectory_kitti", "lo_save_ply",
     # include/lo_pgo.h
@@ -281,6 +282,8 @@ def lib():
     L.lo_debug_counters_ex.argtypes = [vp, C.POINTER(C.c_ulonglong), C.c_int]
     L.lo_debug_live_bytes.argtypes = []
     L.lo_debug_live_bytes.restype = C.c_longlong
+    L.lo_debug_grid.argtypes = [vp, fp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                C.POINTER(C.c_uint32), C.c_size_t, fp, C.c_size_t]
     L.lo_pipeline_status.argtypes = [vp, C.POINTER(C.c_int)]
     L.lo_set_pko_groups.argtypes = [vp, C.c_int]
     L.lo_update_config.argtypes = [vp, C.POINTER(LoConfig)]
@@ -309,8 +312,13 @@ def lib():
                                         C.POINTER(LoBatchRec), C.POINTER(C.c_size_t)]
     L.lo_batch_update_maps.argtypes = [vp, C.POINTER(vp), u8p, fp, C.c_double]
     L.lo_batch_maps_status.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int)]
+    L.lo_batch_sync_points.argtypes = [vp, C.POINTER(vp), u8p]
     L.lo_odom_batch_create.restype = vp
     L.lo_odom_batch_create.argtypes = [C.POINTER(LoOdomConfig), C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_int)]
+    L.lo_odom_batch_create_kdtree.restype = vp
+    L.lo_odom_batch_create_kdtree.argtypes = L.lo_odom_batch_create.argtypes
+    L.lo_odom_batch_kd_reruns.argtypes = [vp, C.c_int]
+    L.lo_odom_kd_reruns.argtypes = [vp]
     L.lo_odom_batch_destroy.restype = None
     L.lo_odom_batch_destroy.argtypes = [vp]
     L.lo_odom_batch_last_error.restype = C.c_char_p

@@ -85,16 +85,23 @@ struct lo_batch {
     // lo_batch_update_maps (lo_devmap.hip): its per-batch state, and how to free it
     void* map_state = nullptr;
     void (*map_state_release)(void*) = nullptr;
+    // lo_batch_sync_points (lo_grid.hip): the same for the batched grid build
+    void* grid_state = nullptr;
+    void (*grid_state_release)(void*) = nullptr;
 };
 
 namespace lo {
 BatchView batch_view(lo_batch* b) {
-    return BatchView{b->ctx.data(), static_cast<int>(b->ctx.size()), b->device, b->stream, b->pending};
+    return BatchView{b->ctx.data(), static_cast<int>(b->ctx.size()), b->device, b->stream, b->pending, b->kd};
 }
 void batch_set_error(lo_batch* b, const char* msg) { b->err = msg; }
 void** batch_map_state(lo_batch* b, void (*release)(void*)) {
     b->map_state_release = release;
     return &b->map_state;
+}
+void** batch_grid_state(lo_batch* b, void (*release)(void*)) {
+    b->grid_state_release = release;
+    return &b->grid_state;
 }
 }  // namespace lo
 
@@ -253,6 +260,7 @@ void lo_batch_destroy(lo_batch* b) {
     (void)hipSetDevice(b->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     if (b->map_state && b->map_state_release) b->map_state_release(b->map_state);
+    if (b->grid_state && b->grid_state_release) b->grid_state_release(b->grid_state);
     if (b->ev0) (void)hipEventDestroy(b->ev0);
     if (b->ev1) (void)hipEventDestroy(b->ev1);
     if (b->ev_go) (void)hipEventDestroy(b->ev_go);

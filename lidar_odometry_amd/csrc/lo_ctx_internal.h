@@ -1,6 +1,7 @@
 // lo_ctx_internal.h — library-internal accessors of an ICP context (C++ linkage, not part of the C ABI).
 #pragma once
 #include <cstdint>
+#include <string>
 
 #include "../../include/lo_icp.h"
 
@@ -55,8 +56,25 @@ struct BatchView {
     int device;
     void* stream;
     bool pending;
+    bool kd;                         // a KDTree-mode batch
 };
 BatchView batch_view(lo_batch* b);
 void batch_set_error(lo_batch* b, const char* msg);
 void** batch_map_state(lo_batch* b, void (*release)(void*));
+// the same kind of slot for the batched grid build (lo_grid.hip: batch_grids_from_device)
+void** batch_grid_state(lo_batch* b, void (*release)(void*));
+
+// ctx_grid_from_device for the jobs of a KDTree batch in one set of launches on the batch stream (lo_batch_sync_points,
+// lo_map.h): src[a] is active job `job`'s point array on its context `c`.  One readback (bounds and raw count of every
+// job) and one synchronise size all grids; each context's grid afterwards equals ctx_grid_from_device's on the same
+// points.  A job whose raw count exceeds its cap keeps its grid and makes the call return LO_ERR_CAPACITY once the
+// other jobs' grids are enqueued (*bad_job: the first such job).  err: the error text.
+struct GridSrc {
+    lo_ctx* c;
+    const float* xyz;
+    const int* count;
+    size_t cap;
+    int job;
+};
+int batch_grids_from_device(lo_batch* b, const GridSrc* src, int n, std::string* err, int* bad_job);
 }  // namespace lo

@@ -1963,9 +1963,39 @@ int bm_status(lo_batch* b, const BatchView& V, lo_devmap* const* maps, int* out,
     return rc;
 }
 
+// RebuildKdTree for the active jobs: the maps' L0 centroids and device counts handed to the batched grid build
+int bm_sync_points(lo_batch* b, const BatchView& V, lo_devmap* const* maps, const unsigned char* active, BatchErr* e) {
+    if (!V.kd) {
+        e->err = "lo_batch_sync_points needs a KDTree-mode batch (use_surfel_correspondence = 0)";
+        return LO_ERR_STATE;
+    }
+    if (V.pending) { e->err = "batch in flight: call lo_batch_result first"; return LO_ERR_STATE; }
+    int rc = bm_check_maps(V, maps, active, e);
+    if (rc != LO_OK) return rc;
+    std::vector<GridSrc> src;
+    for (int j = 0; j < V.count; ++j) {
+        if (!active[j]) continue;
+        const DM& M = maps[j]->M;
+        src.push_back(GridSrc{V.ctx[j], M.c0, M.cnt + C_N0, static_cast<size_t>(M.C0), j});
+    }
+    int bad = -1;
+    rc = batch_grids_from_device(b, src.data(), static_cast<int>(src.size()), &e->err, &bad);
+    if (bad >= 0) maps[bad]->err = std::string("sync_points: ") + lo_last_error(V.ctx[bad]);
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
+
+int lo_batch_sync_points(lo_batch* b, lo_devmap* const* maps, const unsigned char* active) {
+    if (!b) return LO_ERR_ARG;
+    if (!maps || !active) { batch_set_error(b, "null argument"); return LO_ERR_ARG; }
+    BatchErr e;
+    const int rc = bm_sync_points(b, batch_view(b), maps, active, &e);
+    if (rc != LO_OK) batch_set_error(b, e.err.c_str());
+    return rc;
+}
 
 int lo_batch_update_maps(lo_batch* b, lo_devmap* const* maps, const unsigned char* active, const float* T,
                          double max_distance) {

@@ -1,6 +1,7 @@
 // lo_grid.hip — the KDTree variant's point grid: built on the host (grid_build, all_pairs_upload; lo_map_set_points)
 // or on the device (grid_from_device and its k_grid_* kernels: a device map's centroids through ctx_grid_from_device,
-// the loop-closure ICP's device-resident matched cloud through loop_map_from_device).
+// the loop-closure ICP's device-resident matched cloud through loop_map_from_device; the grids of all active jobs of a
+// KDTree batch through batch_grids_from_device and its k_grid_*_b kernels: eight launches, lo_batch_sync_points).
 #include <hipcub/hipcub.hpp>
 
 #include "lo_ctx_def.h"
@@ -141,8 +142,9 @@ namespace lo {
 // ---- the same grid built on the device (ctx_grid_from_device: the device map's L0 centroids) ----
 // Every kernel here clamps the device count to the array's capacity: a corrupt or overflowing count is reported by the
 // host (out[6] carries the raw count) without a read past the array.
-__global__ __launch_bounds__(1024) void k_grid_bounds(const float* __restrict__ xyz, const int* __restrict__ d_count,
-                                                     int cap, float* __restrict__ out) {
+// the bounds of one point array by one 1024-thread workgroup: out[0..2] the minima, [3..5] the maxima, [6] the raw count
+__device__ __forceinline__ void grid_bounds_body(const float* __restrict__ xyz, const int* __restrict__ d_count, int cap,
+                                                 float* __restrict__ out) {
     __shared__ float s[6][16];
     const int m_raw = *d_count, m = min(max(m_raw, 0), cap), tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
@@ -159,21 +161,29 @@ __global__ __launch_bounds__(1024) void k_grid_bounds(const float* __restrict__ 
     }
     if (tid == 0) out[6] = __int_as_float(m_raw);
 }
+__global__ __launch_bounds__(1024) void k_grid_bounds(const float* __restrict__ xyz, const int* __restrict__ d_count,
+                                                     int cap, float* __restrict__ out) {
+    grid_bounds_body(xyz, d_count, cap, out);
+}
 struct GridGeom {
     float h;
     int org[3], dim[3];
 };
 // grid_build's cell of a coordinate: floor(v / h) in fp32, as an int64 (the same operations)
 __device__ __forceinline__ long long grid_cell(float v, float h) { return static_cast<long long>(floorf(v / h)); }
+// point i's cell in the grid, x fastest (grid_build's lin[i])
+__device__ __forceinline__ uint32_t grid_lin(const float* __restrict__ xyz, int i, const GridGeom& g) {
+    const long long x = grid_cell(xyz[3 * i], g.h) - g.org[0], y = grid_cell(xyz[3 * i + 1], g.h) - g.org[1],
+                    z = grid_cell(xyz[3 * i + 2], g.h) - g.org[2];
+    return static_cast<uint32_t>((static_cast<unsigned long long>(z) * g.dim[1] + y) * g.dim[0] + x);
+}
 // occ (nullable): the number of occupied cells (grid_build's `occupied`, for the min_per_cell rule)
 __global__ void k_grid_keys(const float* __restrict__ xyz, const int* __restrict__ d_count, int cap, GridGeom g,
                             uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t* __restrict__ counts,
                             uint32_t* __restrict__ occ) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= min(*d_count, cap)) return;
-    const long long x = grid_cell(xyz[3 * i], g.h) - g.org[0], y = grid_cell(xyz[3 * i + 1], g.h) - g.org[1],
-                    z = grid_cell(xyz[3 * i + 2], g.h) - g.org[2];
-    const uint32_t lin = static_cast<uint32_t>((static_cast<unsigned long long>(z) * g.dim[1] + y) * g.dim[0] + x);
+    const uint32_t lin = grid_lin(xyz, i, g);
     keys[i] = lin;
     vals[i] = static_cast<uint32_t>(i);
     if (atomicAdd(&counts[lin], 1u) == 0u && occ) atomicAdd(occ, 1u);
@@ -193,6 +203,32 @@ int grid_scratch(lo_ctx* c) {
     return LO_OK;
 }
 
+// grid_build's geometry loop from the bounds of m points (floor(v / h) is monotone in v, so the cells' extremes are the
+// extremes' cells): h doubles until the grid fits kKdMaxCells; org / dim out; returns the cell count.
+static size_t grid_fit(const float* bounds, size_t m, float& h, int org[3], int dim[3]) {
+    auto cell = [&](float v) { return static_cast<int64_t>(std::floor(v / h)); };
+    for (;;) {
+        int64_t lo[3], hi[3];
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = m ? cell(bounds[a]) : 0;
+            hi[a] = m ? cell(bounds[3 + a]) : 0;
+        }
+        size_t ncell = 1;
+        bool ok = true;
+        for (int a = 0; a < 3; ++a) {
+            const int64_t d = hi[a] - lo[a] + 1;
+            if (d > static_cast<int64_t>(kKdMaxCells) || lo[a] < INT32_MIN / 2 || hi[a] > INT32_MAX / 2) { ok = false; break; }
+            ncell *= static_cast<size_t>(d);
+            if (ncell > kKdMaxCells) { ok = false; break; }
+        }
+        if (ok) {
+            for (int a = 0; a < 3; ++a) { org[a] = static_cast<int>(lo[a]); dim[a] = static_cast<int>(hi[a] - lo[a] + 1); }
+            return ncell;
+        }
+        h *= 2.0f;
+    }
+}
+
 // grid_build's grid of a device point array, into G.  min_per_cell as grid_build: the cell edge doubles (up to 3
 // times) while the occupied cells hold fewer points on average -- the occupied count is one more 4-byte readback per
 // doubling step.
@@ -208,11 +244,8 @@ int grid_from_device(lo_ctx* c, PointGrid& G, const float* d_xyz, const int* d_c
     std::memcpy(&mi, &S.h_bounds[6], sizeof(int));
     const size_t m = static_cast<size_t>(std::max(mi, 0));
     if (m > cap) { c->err = "ctx_grid_from_device: count beyond the array"; return LO_ERR_CAPACITY; }
-    // grid_build's geometry loop, from the bounds (floor(v / h) is monotone in v, so the cells' extremes are the
-    // extremes' cells)
     float h = 2.0f * c->cfg.voxel_size;
     int org[3] = {0, 0, 0}, dim[3] = {1, 1, 1};
-    auto cell = [&](float v) { return static_cast<int64_t>(std::floor(v / h)); };
     const size_t mm = std::max<size_t>(m, 1);
     LO_HIP(c, G.d_pts.reserve(mm));
     LO_HIP(c, S.d_keys.reserve(4 * mm));                 // keys, vals, sorted keys, sorted vals
@@ -221,23 +254,7 @@ int grid_from_device(lo_ctx* c, PointGrid& G, const float* d_xyz, const int* d_c
     const dim3 grid((mm + 255) / 256), blk(256);
     size_t ncell = 1;
     for (int grow = 0;; ++grow) {
-        for (;;) {
-            int64_t lo[3], hi[3];
-            for (int a = 0; a < 3; ++a) {
-                lo[a] = m ? cell(S.h_bounds[a]) : 0;
-                hi[a] = m ? cell(S.h_bounds[3 + a]) : 0;
-            }
-            ncell = 1;
-            bool ok = true;
-            for (int a = 0; a < 3; ++a) {
-                const int64_t d = hi[a] - lo[a] + 1;
-                if (d > static_cast<int64_t>(kKdMaxCells) || lo[a] < INT32_MIN / 2 || hi[a] > INT32_MAX / 2) { ok = false; break; }
-                ncell *= static_cast<size_t>(d);
-                if (ncell > kKdMaxCells) { ok = false; break; }
-            }
-            if (ok) { for (int a = 0; a < 3; ++a) { org[a] = static_cast<int>(lo[a]); dim[a] = static_cast<int>(hi[a] - lo[a] + 1); } break; }
-            h *= 2.0f;
-        }
+        ncell = grid_fit(S.h_bounds, m, h, org, dim);
         LO_HIP(c, G.d_start.reserve(ncell + 1));
         LO_HIP(c, S.d_counts.reserve(ncell + 1));
         LO_HIP(c, hipMemsetAsync(S.d_counts, 0, (ncell + 1) * sizeof(uint32_t), c->stream));
@@ -345,6 +362,296 @@ int ctx_grid_from_device(lo_ctx* c, const float* d_xyz, const int* d_count, size
     LO_HIP(c, hipSetDevice(c->device));
     const int rc = grid_from_device(c, c->grid, d_xyz, d_count, cap, 0);
     if (rc == LO_OK) c->grid_dev = true;
+    return rc;
+}
+
+// ---- the grids of a batch (lo_batch_sync_points): ctx_grid_from_device for all active jobs in one set of launches ----
+// k_grid_*_b: blockIdx.y = active slot, its job's descriptor read from a device array.  Two host-to-device copies (the
+// jobs' point arrays before the bounds, the grids' descriptors after the readback), one device-to-host copy of seven
+// words per job with the call's one synchronise, and eight launches, whatever the number of jobs:
+//   k_grid_bounds_b      one workgroup per job: grid_bounds_body
+//   k_grid_clear_b       counts[0 .. ncell] = 0
+//   k_grid_keys_b        every point's cell, and its arrival number in the cell (the cell count's atomicAdd)
+//   k_grid_scan_sum_b    exclusive scan of counts into start, three launches: each workgroup sums its chunk of the
+//   k_grid_scan_top_b      job's ncell + 1 counts, one workgroup per job scans the chunk sums, each workgroup scans
+//   k_grid_scan_write_b    its chunk from its offset
+//   k_grid_claim_b       slots[start[cell] + arrival] = point index (arrival order inside a cell: arbitrary)
+//   k_grid_place_b       a point's rank in its cell = the cell's slot entries with a smaller index; the point goes to
+//                        start[cell] + rank -- index order inside a cell, whatever order the atomics landed in
+// Every phase reads what an earlier launch wrote: no kernel fills through atomics and reads the result itself.
+struct GridJob {
+    const float* xyz;                // the points, 3 floats each
+    const int* d_count;              //   *d_count of them on the device (clamped to cap and to m)
+    int cap;
+    int m;                           // the host's copy of the count (what the buffers below are sized for)
+    GridGeom g;
+    uint32_t n;                      // ncell + 1: the words of counts and start
+    uint32_t chunk;                  // scan: words per workgroup (a multiple of kGridScanBlock)
+    uint32_t* counts;                // [n]
+    uint32_t* start;                 // [n]
+    uint32_t* keys;                  // [m] a point's cell (kGridNoCell: none)
+    uint32_t* rank;                  // [m] its arrival number in the cell
+    uint32_t* slots;                 // [m] point indices grouped by cell
+    uint32_t* bsum;                  // [gridDim.x of the scan] chunk sums, then their exclusive scan
+    float4* pts;                     // [m]
+};
+constexpr int kGridScanBlock = 256;
+constexpr int kGridScanMaxBlocks = 1024;         // chunk sums per job: what k_grid_scan_top_b's one workgroup scans
+constexpr int kGridBatchWGs = 65536;             // workgroups per launch over all jobs
+constexpr uint32_t kGridNoCell = 0xFFFFFFFFu;
+
+__device__ __forceinline__ int grid_job_m(const GridJob& J) { return min(min(max(*J.d_count, 0), J.cap), J.m); }
+
+__global__ __launch_bounds__(1024) void k_grid_bounds_b(const GridJob* __restrict__ jobs, float* __restrict__ out) {
+    const GridJob& J = jobs[blockIdx.y];
+    grid_bounds_body(J.xyz, J.d_count, J.cap, out + 7 * blockIdx.y);
+}
+__global__ __launch_bounds__(256) void k_grid_clear_b(const GridJob* __restrict__ jobs) {
+    const GridJob& J = jobs[blockIdx.y];
+    const uint32_t n4 = J.n >> 2, step = gridDim.x * 256u;
+    uint4* c4 = reinterpret_cast<uint4*>(J.counts);      // (a hipMalloc'ed array: 16-byte aligned)
+    for (uint32_t k = blockIdx.x * 256u + threadIdx.x; k < n4; k += step) c4[k] = make_uint4(0u, 0u, 0u, 0u);
+    if (blockIdx.x == 0 && threadIdx.x < (J.n & 3u)) J.counts[4u * n4 + threadIdx.x] = 0u;
+}
+// k_grid_keys' body per job (no occupancy rule: min_per_cell is 0 here).  A cell outside the grid cannot come from the
+// points the bounds were taken of; such a point (a non-finite coordinate, say) is left out instead of counted.
+__global__ __launch_bounds__(256) void k_grid_keys_b(const GridJob* __restrict__ jobs) {
+    const GridJob& J = jobs[blockIdx.y];
+    const int m = grid_job_m(J), step = gridDim.x * 256;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < m; i += step) {
+        uint32_t lin = grid_lin(J.xyz, i, J.g), r = 0u;
+        if (lin < J.n - 1u) r = atomicAdd(&J.counts[lin], 1u);
+        else lin = kGridNoCell;
+        J.keys[i] = lin;
+        J.rank[i] = r;
+    }
+}
+// exclusive scan of one value per thread over a 64 * NW-thread workgroup; total: the workgroup's sum
+template <int NW>
+__device__ __forceinline__ uint32_t grid_block_scan(uint32_t v, uint32_t* s_w, uint32_t& total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t inc = v;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t t = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += t;
+    }
+    if (lane == 63) s_w[w] = inc;
+    __syncthreads();
+    uint32_t off = 0u, tot = 0u;
+    for (int k = 0; k < NW; ++k) {
+        const uint32_t t = s_w[k];
+        if (k < w) off += t;
+        tot += t;
+    }
+    __syncthreads();                                     // s_w is free for the next call
+    total = tot;
+    return off + inc - v;
+}
+__global__ __launch_bounds__(kGridScanBlock) void k_grid_scan_sum_b(const GridJob* __restrict__ jobs) {
+    __shared__ uint32_t s_w[kGridScanBlock / 64];
+    const GridJob& J = jobs[blockIdx.y];
+    const uint64_t b0 = static_cast<uint64_t>(blockIdx.x) * J.chunk;
+    const uint32_t e0 = static_cast<uint32_t>(min(b0 + J.chunk, static_cast<uint64_t>(J.n)));
+    uint32_t sum = 0u;
+    for (uint64_t k = b0 + threadIdx.x; k < e0; k += kGridScanBlock) sum += J.counts[k];
+    uint32_t total;
+    (void)grid_block_scan<kGridScanBlock / 64>(sum, s_w, total);
+    if (threadIdx.x == 0) J.bsum[blockIdx.x] = total;
+}
+__global__ __launch_bounds__(kGridScanMaxBlocks) void k_grid_scan_top_b(const GridJob* __restrict__ jobs, int nblk) {
+    __shared__ uint32_t s_w[kGridScanMaxBlocks / 64];
+    const GridJob& J = jobs[blockIdx.y];
+    const int t = threadIdx.x;
+    const uint32_t v = t < nblk ? J.bsum[t] : 0u;
+    uint32_t total;
+    const uint32_t ex = grid_block_scan<kGridScanMaxBlocks / 64>(v, s_w, total);
+    if (t < nblk) J.bsum[t] = ex;
+}
+__global__ __launch_bounds__(kGridScanBlock) void k_grid_scan_write_b(const GridJob* __restrict__ jobs) {
+    __shared__ uint32_t s_w[kGridScanBlock / 64];
+    const GridJob& J = jobs[blockIdx.y];
+    const uint64_t b0 = static_cast<uint64_t>(blockIdx.x) * J.chunk;
+    if (b0 >= J.n) return;                               // (the whole workgroup: no barrier is skipped by a part of it)
+    const uint32_t e0 = static_cast<uint32_t>(min(b0 + J.chunk, static_cast<uint64_t>(J.n)));
+    uint32_t carry = J.bsum[blockIdx.x];
+    for (uint32_t base = static_cast<uint32_t>(b0); base < e0; base += kGridScanBlock) {
+        const uint32_t k = base + threadIdx.x;
+        const uint32_t v = k < e0 ? J.counts[k] : 0u;
+        uint32_t total;
+        const uint32_t ex = grid_block_scan<kGridScanBlock / 64>(v, s_w, total);
+        if (k < e0) J.start[k] = carry + ex;
+        carry += total;
+    }
+}
+__global__ __launch_bounds__(256) void k_grid_claim_b(const GridJob* __restrict__ jobs) {
+    const GridJob& J = jobs[blockIdx.y];
+    const int m = grid_job_m(J), step = gridDim.x * 256;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < m; i += step) {
+        const uint32_t lin = J.keys[i];
+        if (lin == kGridNoCell) continue;
+        const uint32_t p = J.start[lin] + J.rank[i];
+        if (p < static_cast<uint32_t>(m)) J.slots[p] = static_cast<uint32_t>(i);
+    }
+}
+__global__ __launch_bounds__(256) void k_grid_place_b(const GridJob* __restrict__ jobs) {
+    const GridJob& J = jobs[blockIdx.y];
+    const int m = grid_job_m(J), step = gridDim.x * 256;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < m; i += step) {
+        const uint32_t lin = J.keys[i];
+        if (lin == kGridNoCell) continue;
+        const uint32_t s = J.start[lin], e = min(J.start[lin + 1u], static_cast<uint32_t>(m));
+        uint32_t p = s;
+        for (uint32_t q = s; q < e; ++q) p += J.slots[q] < static_cast<uint32_t>(i) ? 1u : 0u;
+        if (p < static_cast<uint32_t>(m))
+            J.pts[p] = make_float4(J.xyz[3 * i], J.xyz[3 * i + 1], J.xyz[3 * i + 2], __int_as_float(i));
+    }
+}
+
+namespace {
+struct BatchGrids {
+    int device = 0;
+    DevBuf<GridJob> d_jobs;
+    PinnedBuf<GridJob> h_jobs;
+    DevBuf<float> d_bounds;          // 7 words per active slot
+    PinnedBuf<float> h_bounds;
+    DevBuf<uint32_t> d_bsum;         // the scan's chunk sums of all slots (at most kGridBatchWGs workgroups scan)
+    hipEvent_t ev_up = nullptr;      // the last call's second upload has read h_jobs
+    bool up_pending = false;
+};
+void bg_release(void* p) {
+    BatchGrids* S = static_cast<BatchGrids*>(p);
+    (void)hipSetDevice(S->device);
+    if (S->ev_up) (void)hipEventDestroy(S->ev_up);
+    delete S;
+}
+struct GridErr { std::string err; };
+// A buffer that has to grow takes half as much again (at most 4M elements more): a map gains cells and points with
+// every keyframe, and a hipFree + hipMalloc per buffer per job per keyframe costs more than the eight launches (their
+// cost rises with the number of live allocations: B = 1024 keyframes took 256 ms with exact sizes).
+template <class T>
+hipError_t bg_grow(DevBuf<T>& buf, size_t need) {
+    return need <= buf.capacity() ? hipSuccess : buf.reserve(need + std::min(need / 2, size_t(1) << 22));
+}
+
+int bg_run(lo_batch* b, const GridSrc* src, int n, GridErr* e, int* bad_job) {
+    const BatchView V = batch_view(b);
+    LO_HIP(e, hipSetDevice(V.device));
+    void** slot = batch_grid_state(b, bg_release);
+    if (!*slot) {
+        BatchGrids* S = new BatchGrids();
+        S->device = V.device;
+        *slot = S;                                           // owned by the batch from here on
+    }
+    BatchGrids* S = static_cast<BatchGrids*>(*slot);
+    const size_t B = static_cast<size_t>(V.count);
+    if (!S->ev_up) LO_HIP(e, hipEventCreateWithFlags(&S->ev_up, hipEventDisableTiming));
+    LO_HIP(e, S->d_jobs.reserve(B));
+    LO_HIP(e, S->h_jobs.reserve(B));
+    LO_HIP(e, S->d_bounds.reserve(7 * B));
+    LO_HIP(e, S->h_bounds.reserve(7 * B));
+    if (S->up_pending) {                                     // the previous call's upload still reads h_jobs
+        LO_HIP(e, hipEventSynchronize(S->ev_up));
+        S->up_pending = false;
+    }
+    if (n <= 0) return LO_OK;
+    hipStream_t bs = static_cast<hipStream_t>(V.stream);
+    for (int a = 0; a < n; ++a) {
+        GridJob J{};
+        J.xyz = src[a].xyz;
+        J.d_count = src[a].count;
+        J.cap = static_cast<int>(std::min(src[a].cap, static_cast<size_t>(INT32_MAX)));
+        S->h_jobs[a] = J;
+    }
+    LO_HIP(e, hipMemcpyAsync(S->d_jobs, S->h_jobs, sizeof(GridJob) * n, hipMemcpyHostToDevice, bs));
+    hipLaunchKernelGGL(k_grid_bounds_b, dim3(1, n), dim3(1024), 0, bs, S->d_jobs.get(), S->d_bounds.get());
+    LO_HIP(e, hipGetLastError());
+    LO_HIP(e, hipMemcpyAsync(S->h_bounds, S->d_bounds, sizeof(float) * 7 * n, hipMemcpyDeviceToHost, bs));
+    LO_HIP(e, hipStreamSynchronize(bs));
+    // nothing is in flight on the batch stream now (and the contexts are idle, as for every batch call): each job's
+    // geometry, and its buffers grown where they have to
+    int rc = LO_OK, k = 0;
+    size_t max_n = 1, max_m = 1;
+    for (int a = 0; a < n; ++a) {
+        lo_ctx* c = src[a].c;
+        const float* hb = S->h_bounds + 7 * a;
+        int mi = 0;
+        std::memcpy(&mi, &hb[6], sizeof(int));
+        const size_t m = static_cast<size_t>(std::max(mi, 0));
+        if (m > src[a].cap) {
+            c->err = "ctx_grid_from_device: count beyond the array";
+            if (rc == LO_OK) {
+                rc = LO_ERR_CAPACITY;
+                *bad_job = src[a].job;
+                e->err = "job " + std::to_string(src[a].job) + ": " + c->err;
+            }
+            continue;
+        }
+        PointGrid& G = c->grid;
+        DevGridScratch& W = c->gscr;
+        float h = 2.0f * c->cfg.voxel_size;
+        int org[3] = {0, 0, 0}, dim[3] = {1, 1, 1};
+        const size_t ncell = grid_fit(hb, m, h, org, dim), mm = std::max<size_t>(m, 1);
+        LO_HIP(e, bg_grow(G.d_pts, mm));
+        LO_HIP(e, bg_grow(G.d_start, ncell + 1));
+        LO_HIP(e, bg_grow(W.d_keys, 4 * mm));                // (grid_from_device's size: the two forms share it)
+        LO_HIP(e, bg_grow(W.d_counts, ncell + 1));
+        GridJob J = S->h_jobs[a];
+        J.m = static_cast<int>(m);
+        J.g = GridGeom{h, {org[0], org[1], org[2]}, {dim[0], dim[1], dim[2]}};
+        J.n = static_cast<uint32_t>(ncell + 1);
+        J.counts = W.d_counts;
+        J.start = G.d_start;
+        J.keys = W.d_keys;
+        J.rank = J.keys + mm;
+        J.slots = J.rank + mm;
+        J.pts = G.d_pts;
+        S->h_jobs[k++] = J;                                  // (k <= a: entry a has been read)
+        max_n = std::max(max_n, ncell + 1);
+        max_m = std::max(max_m, mm);
+        G.m = static_cast<int>(m);
+        G.has_order = false;
+        G.all = false;
+        G.h = h;
+        for (int x = 0; x < 3; ++x) { G.org[x] = org[x]; G.dim[x] = dim[x]; }
+        c->grid_dev = true;
+    }
+    if (k == 0) return rc;
+    // launch sizes from the largest job under the workgroup budget; the scan's chunk count is common to all jobs
+    const unsigned per_job = static_cast<unsigned>(std::max(1, kGridBatchWGs / k));
+    auto blocks = [&](size_t items, size_t per) {
+        return static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>(per_job, (items + per - 1) / per)));
+    };
+    const unsigned nblk = std::min(blocks(max_n, 8 * kGridScanBlock), static_cast<unsigned>(kGridScanMaxBlocks));
+    LO_HIP(e, S->d_bsum.reserve(std::max(static_cast<size_t>(kGridBatchWGs), B)));      // >= nblk * k
+    for (int a = 0; a < k; ++a) {
+        GridJob& J = S->h_jobs[a];
+        const uint32_t per = (J.n + nblk - 1) / nblk;
+        J.chunk = (per + kGridScanBlock - 1) / kGridScanBlock * kGridScanBlock;
+        J.bsum = S->d_bsum + static_cast<size_t>(a) * nblk;
+    }
+    LO_HIP(e, hipMemcpyAsync(S->d_jobs, S->h_jobs, sizeof(GridJob) * k, hipMemcpyHostToDevice, bs));
+    LO_HIP(e, hipEventRecord(S->ev_up, bs));
+    S->up_pending = true;
+    const GridJob* J = S->d_jobs;
+    const dim3 pgrid(blocks(max_m, 256), k), cgrid(blocks(max_n, 16 * 256), k), sgrid(nblk, k), blk(256);
+    hipLaunchKernelGGL(k_grid_clear_b, cgrid, blk, 0, bs, J);
+    hipLaunchKernelGGL(k_grid_keys_b, pgrid, blk, 0, bs, J);
+    hipLaunchKernelGGL(k_grid_scan_sum_b, sgrid, dim3(kGridScanBlock), 0, bs, J);
+    hipLaunchKernelGGL(k_grid_scan_top_b, dim3(1, k), dim3(kGridScanMaxBlocks), 0, bs, J, static_cast<int>(nblk));
+    hipLaunchKernelGGL(k_grid_scan_write_b, sgrid, dim3(kGridScanBlock), 0, bs, J);
+    hipLaunchKernelGGL(k_grid_claim_b, pgrid, blk, 0, bs, J);
+    hipLaunchKernelGGL(k_grid_place_b, pgrid, blk, 0, bs, J);
+    LO_HIP(e, hipGetLastError());
+    return rc;
+}
+}  // namespace
+
+int batch_grids_from_device(lo_batch* b, const GridSrc* src, int n, std::string* err, int* bad_job) {
+    GridErr e;
+    int bad = -1;
+    const int rc = bg_run(b, src, n, &e, &bad);
+    if (err) *err = e.err;
+    if (bad_job) *bad_job = bad;
     return rc;
 }
 

@@ -376,6 +376,33 @@ int lo_debug_counters(lo_ctx* c, unsigned long long out[16]) {
     return LO_OK;
 }
 
+int lo_debug_grid(lo_ctx* c, float* h, int org[3], int dim[3], int* m, uint32_t* start, size_t start_cap, float* pts4,
+                  size_t pts_cap) {
+    if (!c) return LO_ERR_ARG;
+    if (!c->kd) { c->err = "lo_debug_grid needs use_surfel_correspondence = 0"; return LO_ERR_STATE; }
+    LO_HIP(c, sync_all(c));
+    LO_HIP(c, hipDeviceSynchronize());                   // a batch stream may have built the grid
+    const PointGrid& G = c->grid;
+    if (h) *h = G.h;
+    for (int a = 0; a < 3; ++a) {
+        if (org) org[a] = G.org[a];
+        if (dim) dim[a] = G.dim[a];
+    }
+    if (m) *m = G.m;
+    const size_t ncell = G.all ? 0 : static_cast<size_t>(G.dim[0]) * G.dim[1] * G.dim[2];
+    const size_t ns = G.all ? 0 : ncell + 1, np = static_cast<size_t>(std::max(G.m, 0));
+    if ((start && start_cap < ns) || (pts4 && pts_cap < np)) { c->err = "lo_debug_grid: output too small"; return LO_ERR_CAPACITY; }
+    if (start && ns > 0) {
+        if (G.d_start.capacity() < ns) { c->err = "lo_debug_grid: no grid yet"; return LO_ERR_STATE; }
+        LO_HIP(c, hipMemcpy(start, G.d_start, ns * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    if (pts4 && np > 0) {
+        if (G.d_pts.capacity() < np) { c->err = "lo_debug_grid: no grid yet"; return LO_ERR_STATE; }
+        LO_HIP(c, hipMemcpy(pts4, G.d_pts, np * sizeof(float4), hipMemcpyDeviceToHost));
+    }
+    return LO_OK;
+}
+
 int lo_debug_counters_ex(lo_ctx* c, unsigned long long* out, int n) {
     if (!c || !out || n < 1 || n > 24) return LO_ERR_ARG;
     LO_HIP(c, sync_all(c));

@@ -438,6 +438,7 @@ int lo_odom_save_map_ply(lo_odometry* o, const char* path, float voxel_size) {
 }
 
 size_t lo_odom_keyframe_count(const lo_odometry* o) { return o ? o->keyframes : 0; }
+int lo_odom_kd_reruns(const lo_odometry* o) { return o ? lo_kd_reruns(o->icp) : -1; }
 size_t lo_odom_map_surfels(const lo_odometry* o) {
     if (!o) return 0;
     if (o->dmap) {
@@ -451,8 +452,9 @@ size_t lo_odom_map_surfels(const lo_odometry* o) {
 }  // extern "C"
 
 // ================================================================================================== B sequences
-// lo_odom_batch_*: lo_odom_process for `count` sequences in lockstep (surfel mode, no loop closure), joined from the
-// batch's pieces: one batched filter, one batched optimize and one batched map update per call, and per job the same
+// lo_odom_batch_*: lo_odom_process for `count` sequences in lockstep (either correspondence mode, no loop closure),
+// joined from the batch's pieces: one batched filter, one batched optimize and one batched map update (KDTree mode: and
+// one batched grid build) per call, and per job the same
 // lo::FrameState bookkeeping on the same values -- so job j's poses, keyframes, iterations and guesses are those of a
 // lo_odometry fed sequence j alone.
 struct lo_odom_batch {
@@ -485,8 +487,12 @@ static int batch_keyframes(lo_odom_batch* o, lo_odom_frame* info) {
     }
     if (!any) return LO_OK;
     const auto t0 = std::chrono::steady_clock::now();
-    const int rc = lo_batch_update_maps(o->batch, o->maps.data(), o->active.data(), o->kf12.data(), o->cfg.max_range * 1.2);
+    int rc = lo_batch_update_maps(o->batch, o->maps.data(), o->active.data(), o->kf12.data(), o->cfg.max_range * 1.2);
     if (rc != LO_OK) { o->err = std::string("keyframe map update: ") + lo_batch_last_error(o->batch); return rc; }
+    if (!o->cfg.icp.use_surfel_correspondence) {             // RebuildKdTree (Estimator.cpp:460-462) for the same jobs
+        rc = lo_batch_sync_points(o->batch, o->maps.data(), o->active.data());
+        if (rc != LO_OK) { o->err = std::string("keyframe grid build: ") + lo_batch_last_error(o->batch); return rc; }
+    }
     const double ms = ms_since(t0);
     o->status_due = true;
     for (int j = 0; j < o->count; ++j) {
@@ -507,21 +513,26 @@ static int batch_map_status(lo_odom_batch* o) {
     return rc;
 }
 
-extern "C" {
-
-lo_odom_batch* lo_odom_batch_create(const lo_odom_config* cfg, int count, int device, size_t max_l0, int* err) {
+// lo_odom_batch_create (kdtree = false) and lo_odom_batch_create_kdtree (true): one constructor, the config's
+// correspondence mode checked against the entry point's
+static lo_odom_batch* odom_batch_create(const lo_odom_config* cfg, int count, int device, size_t max_l0, int* err,
+                                        bool kdtree) {
+    const char* who = kdtree ? "lo_odom_batch_create_kdtree" : "lo_odom_batch_create";
     auto fail = [&](int rc, const std::string& msg, lo_odom_batch* o) -> lo_odom_batch* {
         g_odom_batch_create_err = msg;
-        std::fprintf(stderr, "lo_odom_batch_create: %s\n", msg.c_str());
+        std::fprintf(stderr, "%s: %s\n", who, msg.c_str());
         lo_odom_batch_destroy(o);
         if (err) *err = rc;
         return nullptr;
     };
     if (!cfg || count < 1 || count > 65535 || cfg->point_stride < 1 || !(cfg->filter_voxel_size > 0.0f))
         return fail(LO_ERR_ARG, "need a config, 1..65535 sequences, point_stride >= 1 and filter_voxel_size > 0", nullptr);
-    if (!cfg->icp.use_surfel_correspondence)
-        return fail(LO_ERR_ARG, "KDTree-mode config: the batched frame loop is surfel mode only (the per-context "
-                                "lo_devmap_sync_points has no batched form)", nullptr);
+    if (!kdtree && !cfg->icp.use_surfel_correspondence)
+        return fail(LO_ERR_ARG, "KDTree-mode config: lo_odom_batch_create is surfel mode only (the KDTree frame loop "
+                                "is lo_odom_batch_create_kdtree)", nullptr);
+    if (kdtree && cfg->icp.use_surfel_correspondence)
+        return fail(LO_ERR_ARG, "surfel-mode config: lo_odom_batch_create_kdtree is KDTree mode only "
+                                "(use_surfel_correspondence = 0; the surfel frame loop is lo_odom_batch_create)", nullptr);
     lo_odom_batch* o = new (std::nothrow) lo_odom_batch();
     if (!o) return fail(LO_ERR_ARG, "allocation", nullptr);
     o->cfg = *cfg;
@@ -553,6 +564,16 @@ lo_odom_batch* lo_odom_batch_create(const lo_odom_config* cfg, int count, int de
     o->early.assign(B, 0);
     if (err) *err = LO_OK;
     return o;
+}
+
+extern "C" {
+
+lo_odom_batch* lo_odom_batch_create(const lo_odom_config* cfg, int count, int device, size_t max_l0, int* err) {
+    return odom_batch_create(cfg, count, device, max_l0, err, false);
+}
+
+lo_odom_batch* lo_odom_batch_create_kdtree(const lo_odom_config* cfg, int count, int device, size_t max_l0, int* err) {
+    return odom_batch_create(cfg, count, device, max_l0, err, true);
 }
 
 void lo_odom_batch_destroy(lo_odom_batch* o) {
@@ -664,6 +685,10 @@ int lo_odom_batch_flush(lo_odom_batch* o) {
 
 size_t lo_odom_batch_keyframe_count(const lo_odom_batch* o, int job) {
     return (o && job >= 0 && job < o->count) ? o->keyframes[job] : 0;
+}
+
+int lo_odom_batch_kd_reruns(const lo_odom_batch* o, int job) {
+    return (o && job >= 0 && job < o->count) ? lo_kd_reruns(o->ctx[job]) : -1;
 }
 
 }  // extern "C"

@@ -559,6 +559,20 @@ class BatchOptimizer:
                                                act.ctypes.data_as(C.POINTER(C.c_uint8)), _fptr(T),
                                                float(max_distance)))
 
+    def sync_points(self, maps, active=None):
+        """RebuildKdTree for a KDTree batch's keyframes (lo_batch_sync_points): for each job j with ``active[j]``
+        (default: every job), what ``lo_devmap_sync_points(maps[j])`` does -- optimizer j's correspondence grid rebuilt
+        from map j's L0 centroids -- for all active jobs in one set of launches on the batch stream, behind a
+        preceding ``update_maps``.  One readback and one synchronise for all jobs; ``maps_status`` waits for the
+        grids."""
+        B = len(self.optimizers)
+        act = np.ones(B, np.uint8) if active is None else \
+            np.ascontiguousarray(np.asarray(active).astype(bool).astype(np.uint8))
+        if act.shape != (B,):
+            raise ValueError(f"need {B} active flags")
+        self._check(lib().lo_batch_sync_points(self._b, self._map_handles(maps),
+                                               act.ctypes.data_as(C.POINTER(C.c_uint8))))
+
     def maps_status(self, maps):
         """Waits for the batch stream and returns every job's map status in one copy (lo_batch_maps_status):
         ``LO_OK`` or ``LO_ERR_CAPACITY`` per job (an update that overflowed a capacity aborted)."""

@@ -190,6 +190,11 @@ class LidarOdometry:
         return int(lib().lo_odom_keyframe_count(self._o))
 
     @property
+    def kd_reruns(self) -> int:
+        """Scans run again with the kd visit order after a deciding distance tie (lo_kd_reruns; KDTree mode)."""
+        return int(lib().lo_odom_kd_reruns(self._o))
+
+    @property
     def map_surfels(self) -> int:
         return int(lib().lo_odom_map_surfels(self._o))
 
@@ -197,8 +202,21 @@ class LidarOdometry:
 class BatchLidarOdometry:
     """B sensor streams on one GPU in lockstep (lo_odom_batch_*): ``process(raws)`` takes one raw scan per sequence
     and returns one 3x4 world pose and one FrameInfo per sequence.  Each sequence's poses, keyframes, iteration counts
-    and guesses equal a ``LidarOdometry`` fed that sequence alone with the same settings.  Surfel mode only
-    (``use_surfel_correspondence=False`` raises), no loop closure.  ``max_l0``: every sequence's device-map capacity."""
+    and guesses equal a ``LidarOdometry`` fed that sequence alone with the same settings.  The constructor is surfel
+    mode only (``use_surfel_correspondence=False`` raises); ``BatchLidarOdometry.kdtree(count, ...)`` is the same loop
+    for KDTree-mode sequences (lo_odom_batch_create_kdtree).  No loop closure.  ``max_l0``: every sequence's
+    device-map capacity."""
+
+    _create = "lo_odom_batch_create"
+
+    @classmethod
+    def kdtree(cls, count: int, **kwargs):
+        """The frame loop for ``count`` KDTree-mode sequences (``use_surfel_correspondence = 0``): the same keywords as
+        the constructor minus ``use_surfel_correspondence``; every keyframe's grids are rebuilt in one batched call
+        (lo_batch_sync_points) after the batched map update."""
+        if "use_surfel_correspondence" in kwargs:
+            raise TypeError("BatchLidarOdometry.kdtree() takes no use_surfel_correspondence")
+        return _KdtreeBatchLidarOdometry(count, use_surfel_correspondence=False, **kwargs)
 
     def __init__(self, count: int, device: int = 0, max_points: int = 1 << 17, use_surfel_correspondence: bool = True,
                  point_stride: int = 8, voxel_size: float = 0.5, map_voxel_size: float = 0.5, max_range: float = 100.0,
@@ -217,12 +235,12 @@ class BatchLidarOdometry:
         err = C.c_int(0)
         self._L = lib()
         self.count = int(count)
-        self._o = self._L.lo_odom_batch_create(C.byref(cfg), self.count, int(device), int(max_l0), C.byref(err))
+        self._o = getattr(self._L, self._create)(C.byref(cfg), self.count, int(device), int(max_l0), C.byref(err))
         if not self._o:
             why = self._L.lo_odom_batch_last_error(None).decode()
             if err.value == _lib.LO_ERR_ARG:
-                raise ValueError(f"lo_odom_batch_create: {why} (code {err.value})")
-            raise RuntimeError(f"lo_odom_batch_create failed (code {err.value}): {why}")
+                raise ValueError(f"{self._create}: {why} (code {err.value})")
+            raise RuntimeError(f"{self._create} failed (code {err.value}): {why}")
         if initial_poses is not None:
             for j, P in enumerate(initial_poses):
                 if P is None:
@@ -268,6 +286,15 @@ class BatchLidarOdometry:
 
     def keyframes(self, job: int) -> int:
         return int(self._L.lo_odom_batch_keyframe_count(self._o, int(job)))
+
+    def kd_reruns(self, job: int) -> int:
+        """Scans of sequence ``job`` run again with the kd visit order after a deciding distance tie (lo_kd_reruns)."""
+        return int(self._L.lo_odom_batch_kd_reruns(self._o, int(job)))
+
+
+class _KdtreeBatchLidarOdometry(BatchLidarOdometry):
+    """What ``BatchLidarOdometry.kdtree`` returns: the same object created through lo_odom_batch_create_kdtree."""
+    _create = "lo_odom_batch_create_kdtree"
 
 
 __all__ = ["LidarOdometry", "BatchLidarOdometry", "FrameInfo", "LoopConfig", "LoopEvent", "_lib"]

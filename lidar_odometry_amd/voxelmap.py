@@ -164,6 +164,10 @@ class DeviceVoxelMap:
                                  np.asarray(T, np.float32).reshape(12)).reshape(12)
         self._check(self._L.lo_devmap_apply_transform(self._h, _f(t)))
 
+    def sync_points(self):
+        """KDTree-mode context: its correspondence grid rebuilt from this map's L0 centroids (lo_devmap_sync_points)."""
+        self._check(self._L.lo_devmap_sync_points(self._h))
+
     def status(self) -> int:
         """lo_devmap_status: 0, or LO_ERR_CAPACITY when an update overflowed a capacity / met a key beyond +-2^20."""
         return int(self._L.lo_devmap_status(self._h))

@@ -3,6 +3,7 @@
 
     python scripts/batch_map_bench.py [--batches 64,256,1024] [--loop-batches 64] [--ways batched,per_context]
                                       [--passes 9] [--warmup 2] [--parent-json FILE] [--out profiles/batch_map_bench.json]
+                                      [--kdtree]
 
 Map updates.  B contexts (max_points 2^14) with one device map each (max_l0 2^15); every pass is one keyframe for all
 B maps: frame 2 p of the 40-frame HDL-64-like sequence of the tests (~3.7k feature points at stride 8, voxel 0.5) at
@@ -20,6 +21,12 @@ in fast mode.  A way's window is its calls for the frame plus its own drain (lo_
 every loop), so the keyframe's map update is inside the window of the way that enqueued it; the ways take turns to go
 first.  --ways per_context times the solo loops alone: that is the run to make in a checkout of the parent commit,
 and --parent-json FILE merges its figures (map updates and frame loop) into this run's output.
+
+--kdtree.  The same two legs for KDTree-mode contexts (use_surfel_correspondence = 0), where every keyframe also
+rebuilds the context's correspondence grid: batched is lo_batch_update_maps + lo_batch_sync_points +
+lo_batch_maps_status, per_context is B x (lo_devmap_update_from_scan + lo_devmap_sync_points) and lo_sync on every
+context; the frame loop is BatchLidarOdometry.kdtree beside B KDTree LidarOdometry loops.  Same windows, same drains;
+the default --out becomes profiles/batch_kdtree_loop_bench.json.
 """
 from __future__ import annotations
 
@@ -35,7 +42,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from lidar_odometry_amd import BatchOptimizer, IterativeClosestPointOptimizer, lib, synth  # noqa: E402
+from lidar_odometry_amd import BatchOptimizer, ICPConfig, IterativeClosestPointOptimizer, lib, synth  # noqa: E402
 from lidar_odometry_amd.voxelmap import DeviceVoxelMap  # noqa: E402
 
 STRIDE, VOXEL, RADIUS = 8, 0.5, 120.0
@@ -48,8 +55,9 @@ def stats(v):
 
 
 class MapSet:
-    def __init__(self, B):
-        self.ctxs = [IterativeClosestPointOptimizer(max_points=MAXP) for _ in range(B)]
+    def __init__(self, B, kdtree=False):
+        self.ctxs = [IterativeClosestPointOptimizer(ICPConfig(use_surfel_correspondence=not kdtree), max_points=MAXP)
+                     for _ in range(B)]
         self.batch = BatchOptimizer(self.ctxs)
         self.maps = [DeviceVoxelMap(c, VOXEL, 3, 0.1, max_l0=MAX_L0, max_points=MAXP) for c in self.ctxs]
 
@@ -61,19 +69,23 @@ class MapSet:
             c.close()
 
 
-def run_maps(B, ways, scans, poses, passes, warmup):
+def run_maps(B, ways, scans, poses, passes, warmup, kdtree=False):
     L = lib()
     fp = C.POINTER(C.c_float)
-    sets = {w: MapSet(B) for w in ways}
+    sets = {w: MapSet(B, kdtree) for w in ways}
     try:
         def batched(S, T):
             S.batch.update_maps(S.maps, [1] * B, [T] * B, RADIUS)
+            if kdtree:
+                S.batch.sync_points(S.maps)
             assert S.batch.maps_status(S.maps) == [0] * B
 
         def per_context(S, T):
             p = np.ascontiguousarray(T[:3].astype(np.float32).reshape(12))
             for m in S.maps:
                 assert L.lo_devmap_update_from_scan(m._h, p.ctypes.data_as(fp), RADIUS) == 0
+                if kdtree:
+                    assert L.lo_devmap_sync_points(m._h) == 0
             for c in S.ctxs:
                 assert L.lo_sync(c.ctx) == 0
 
@@ -100,16 +112,16 @@ def run_maps(B, ways, scans, poses, passes, warmup):
             S.close()
 
 
-def run_loop(B, ways, raws, T0, exact, warmup):
+def run_loop(B, ways, raws, T0, exact, warmup, kdtree=False):
     """Per frame and way: the way's calls for the frame plus its own drain (flush: the keyframe's map update done), so a
     window holds all of its frame's work and nothing of the other way's: both ways are drained before every window, and
     the ways take turns to go first."""
     from lidar_odometry_amd import odometry
     os.environ["LO_DEVMAP_MAX_L0"] = str(MAX_L0)
-    solos = [odometry.LidarOdometry(max_points=MAXP, initial_pose=T0, exact=exact) for _ in range(B)] \
-        if "per_context" in ways else []
-    bo = odometry.BatchLidarOdometry(B, max_points=MAXP, initial_poses=[T0] * B, exact=exact, max_l0=MAX_L0) \
-        if "batched" in ways else None
+    solos = [odometry.LidarOdometry(max_points=MAXP, initial_pose=T0, exact=exact, use_surfel_correspondence=not kdtree)
+             for _ in range(B)] if "per_context" in ways else []
+    make = odometry.BatchLidarOdometry.kdtree if kdtree and "batched" in ways else odometry.BatchLidarOdometry
+    bo = make(B, max_points=MAXP, initial_poses=[T0] * B, exact=exact, max_l0=MAX_L0) if "batched" in ways else None
     try:
         res = {}
 
@@ -183,8 +195,11 @@ def main():
     ap.add_argument("--frames", type=int, default=12)
     ap.add_argument("--parent-json", default=None,
                     help="the JSON of a --ways per_context run in a checkout of the parent commit: merged into --out")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_map_bench.json"))
+    ap.add_argument("--kdtree", action="store_true", help="KDTree-mode contexts: every keyframe also rebuilds the grid")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "batch_kdtree_loop_bench.json" if args.kdtree else "batch_map_bench.json")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("no GPU: this measurement has no CPU form")
@@ -192,14 +207,16 @@ def main():
     ways = [w for w in args.ways.split(",") if w]
     if "batched" in ways and not hasattr(lib(), "lo_batch_update_maps"):
         raise SystemExit("this library has no lo_batch_update_maps: run with --ways per_context")
+    if args.kdtree and "batched" in ways and not hasattr(lib(), "lo_batch_sync_points"):
+        raise SystemExit("this library has no lo_batch_sync_points: run with --ways per_context")
     n = args.warmup + args.passes
     seq = synth.KittiLikeSequence(seed=7, n_frames=2 * n + 1)
     scans = [np.ascontiguousarray(seq.scan(2 * p, device="cuda")) for p in range(n)]
     poses = [seq.poses[2 * p] for p in range(n)]
     out = {"device": torch.cuda.get_device_name(0), "stride": STRIDE,
-           "voxel_size": VOXEL, "max_l0": MAX_L0, "map_updates": [], "frame_loop": []}
+           "voxel_size": VOXEL, "max_l0": MAX_L0, "kdtree": bool(args.kdtree), "map_updates": [], "frame_loop": []}
     for B in (int(v) for v in args.batches.split(",") if v):
-        r = run_maps(B, ways, scans, poses, args.passes, args.warmup)
+        r = run_maps(B, ways, scans, poses, args.passes, args.warmup, args.kdtree)
         print(json.dumps(r), flush=True)
         out["map_updates"].append(r)
     if "batched" not in ways or hasattr(lib(), "lo_odom_batch_process"):
@@ -207,7 +224,7 @@ def main():
         raws = [np.ascontiguousarray(ramp.scan(k, device="cuda")) for k in range(args.frames)]
         for B in (int(v) for v in args.loop_batches.split(",") if v):
             for exact in (True, False):
-                r = run_loop(B, ways, raws, ramp.poses[0], exact, args.warmup)
+                r = run_loop(B, ways, raws, ramp.poses[0], exact, args.warmup, args.kdtree)
                 print(json.dumps(r), flush=True)
                 out["frame_loop"].append(r)
     if args.parent_json:
