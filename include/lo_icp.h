@@ -394,6 +394,20 @@ int lo_seq_sum_f64(lo_ctx* ctx, const double* x, size_t n, int sort, double* out
  * columns": chunk sums, classification, walk).  n <= 4M (the largest scan).  stats (nullable): segment heads, segments
  * summed term by term, chunks run term by term (more heads than a chunk's record list holds), device microseconds. */
 int lo_seq_sum_f32(lo_ctx* ctx, const float* x, size_t n, float* out_sum, long long stats[4]);
+/* Parity entry point of the reference-exact GN solve (IterativeClosestPointOptimizer.cpp:417-448: fp32 LDLT, SO3::Exp,
+ * the re-projected right-update): n systems of 43 totals (H row-major, g, cost) and 12 pose floats each, solved on the
+ * device by the one-lane form and by the wave-cooperative form the PKO launch's exact candidates use.  out_lane and
+ * out_wave receive 19 words per system: the raw bits of the new pose (12), delta (6) and the convergence flag. */
+int lo_exact_solve_both(lo_ctx* ctx, const float* totals, const float* poses, size_t n, double tol_t, double tol_r,
+                        uint32_t* out_lane, uint32_t* out_wave);
+/* Diagnostic (tests): the records the last PKO launch's candidates left -- num_alpha_segments + 1 records of 48 floats:
+ * pose[12] | cost | H upper triangle[21] | g[6] | delta[6] | conv | pad.  Only the launches that pre-solve their
+ * candidates write them (exact mode: the fused candidate path), so a GN step found here was solved there.  Syncs the
+ * context's streams.  Returns the number of records.  LO_ERR_STATE while the record buffer is not allocated (it is
+ * allocated with the speculative normal equations by the first optimize with the adaptive M-estimator on, and dropped
+ * by lo_update_config); an allocated buffer that no launch has written yet holds undefined words, so a caller matches
+ * the records against a logged GN step instead of reading them as such.  LO_ERR_CAPACITY when cap_words is too small. */
+int lo_debug_cand_records(lo_ctx* ctx, float* out, size_t cap_words);
 /* Diagnostic: 16 device counters (phase timestamps of the -DLO_PKO_STAMPS build; zeros otherwise). */
 int lo_debug_counters(lo_ctx* ctx, unsigned long long out[16]);
 /* Diagnostic: the first n (<= 24) device counters. */

@@ -1,6 +1,50 @@
 // lo_hooks.hip — entry points that exist for tests and measurements: the parity hooks (correspondences, kNN, PKO
 // scale, normal equations, sequential sums), stage timing, the kernel benchmarks and the debug counters.
+#include "lo_device.h"   // first: the HIP runtime's device memcpy has to be declared before <cstring> names std::memcpy
 #include "lo_ctx_def.h"
+#include "lo_exact.h"
+
+namespace lo {
+
+// Parity hook of the wave-cooperative solve (lo_exact.h exact_solve_step_wave): one wave per system runs the one-lane
+// exact_solve_step on lane 0 and the wave form on all 64 lanes, from the same 43 totals and pose; the raw bits of
+// pn[12], delta[6] and conv go to out[sys] (one lane) and out[n + sys] (wave), kSolveWords words each.
+constexpr int kSolveWords = 19;
+__global__ __launch_bounds__(kWave) void k_solve_both(const float* __restrict__ totals, const float* __restrict__ poses,
+                                                      int n, double tol_t, double tol_r, uint32_t* __restrict__ out) {
+    const int sys = blockIdx.x, lane = threadIdx.x;
+    if (sys >= n) return;
+    __shared__ float s_tot[kExactTerms];
+    if (lane < kExactTerms) s_tot[lane] = totals[static_cast<size_t>(sys) * kExactTerms + lane];
+    float pose[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) pose[k] = poses[static_cast<size_t>(sys) * 12 + k];
+    __syncthreads();
+    if (lane == 0) {
+        float tot[kExactTerms], pn[12], delta[6];
+#pragma unroll
+        for (int k = 0; k < kExactTerms; ++k) tot[k] = s_tot[k];
+        const bool conv = exact_solve_step(tot, pose, tol_t, tol_r, pn, delta);
+        uint32_t* o = out + static_cast<size_t>(sys) * kSolveWords;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) o[k] = __float_as_uint(pn[k]);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) o[12 + k] = __float_as_uint(delta[k]);
+        o[18] = conv ? 1u : 0u;
+    }
+    float pn[12], delta[6];
+    const bool conv = exact_solve_step_wave(s_tot, pose, tol_t, tol_r, lane, pn, delta);
+    if (lane == 0) {
+        uint32_t* o = out + (static_cast<size_t>(n) + sys) * kSolveWords;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) o[k] = __float_as_uint(pn[k]);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) o[12 + k] = __float_as_uint(delta[k]);
+        o[18] = conv ? 1u : 0u;
+    }
+}
+
+}  // namespace lo
 
 extern "C" {
 
@@ -365,6 +409,41 @@ int lo_seq_sum_f32(lo_ctx* c, const float* x, size_t n, float* out_sum, long lon
         stats[3] = static_cast<long long>(ms * 1e3);      // microseconds of the three launches
     }
     return LO_OK;
+}
+
+int lo_exact_solve_both(lo_ctx* c, const float* totals, const float* poses, size_t n, double tol_t, double tol_r,
+                        uint32_t* out_lane, uint32_t* out_wave) {
+    if (!c || n == 0 || n > (1u << 20) || !totals || !poses || !out_lane || !out_wave) return LO_ERR_ARG;
+    LO_HIP(c, hipSetDevice(c->device));
+    const size_t tb = n * kExactTerms * sizeof(float), pb = n * 12 * sizeof(float), ob = n * kSolveWords * sizeof(uint32_t);
+    DevBuf<char> buf;
+    LO_HIP(c, buf.reserve(tb + pb + 2 * ob));
+    char* d = buf;
+    float* d_tot = reinterpret_cast<float*>(d);
+    float* d_pose = reinterpret_cast<float*>(d + tb);
+    uint32_t* d_out = reinterpret_cast<uint32_t*>(d + tb + pb);
+    hipError_t e = hipMemcpy(d_tot, totals, tb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_pose, poses, pb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_solve_both, dim3(static_cast<unsigned>(n)), dim3(kWave), 0, c->stream, d_tot, d_pose,
+                           static_cast<int>(n), tol_t, tol_r, d_out);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(out_lane, d_out, ob, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_wave, d_out + n * kSolveWords, ob, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { c->err = std::string("lo_exact_solve_both: ") + hipGetErrorString(e); return LO_ERR_HIP; }
+    return LO_OK;
+}
+
+int lo_debug_cand_records(lo_ctx* c, float* out, size_t cap_words) {
+    if (!c || !out) return LO_ERR_ARG;
+    const size_t cand = static_cast<size_t>(c->cfg.num_alpha_segments) + 1, words = cand * kCandWords;
+    if (!c->d_acc_part || c->d_cand_rec.capacity() < words) { c->err = "lo_debug_cand_records: no records yet"; return LO_ERR_STATE; }
+    if (cap_words < words) { c->err = "lo_debug_cand_records: output too small"; return LO_ERR_CAPACITY; }
+    LO_HIP(c, sync_all(c));
+    LO_HIP(c, hipMemcpy(out, c->d_cand_rec, words * sizeof(float), hipMemcpyDeviceToHost));
+    return static_cast<int>(cand);
 }
 
 int lo_debug_counters(lo_ctx* c, unsigned long long out[16]) {

@@ -890,23 +890,22 @@ __device__ void acc_candidate_exact(const KParams& P, double scale, int c, float
 #ifdef LO_PKO_STAMPS
     if (tid == 0) atomicMax(&P.st->dbg[15], __builtin_amdgcn_s_memrealtime());   // the last candidate's sums end
 #endif
-    if (tid == 0) {
-        float tot[kExactTerms], pn[12], delta[6];
-#pragma unroll
-        for (int k = 0; k < kExactTerms; ++k) tot[k] = s_tot[k];
+    if (tid < kWave) {                       // wave 0 solves across its lanes (lo_exact.h exact_solve_step_wave)
+        float pn[12], delta[6];
 #ifdef LO_PKO_STAMPS
         const unsigned long long sv0 = __builtin_amdgcn_s_memtime(), sr0 = __builtin_amdgcn_s_memrealtime();
 #endif
-        const bool conv = exact_solve_step(tot, T, P.tol_t, P.tol_r, pn, delta);
+        // (every lane of wave 0 is here: the branch above is on the wave's index, as the wave form requires)
+        const bool conv = exact_solve_step_wave(s_tot, T, P.tol_t, P.tol_r, tid, pn, delta);
 #ifdef LO_PKO_STAMPS
-        if (c == 0) {                        // diagnostic: candidate 0's solve in shader cycles (dbg[8]) and in
+        if (c == 0 && tid == 0) {            // diagnostic: candidate 0's solve in shader cycles (dbg[8]) and in
             const float keep = pn[0] + delta[0];   // s_memrealtime ticks (dbg[9], 100 MHz): the launch's clock
             asm volatile("" :: "v"(keep));
             P.st->dbg[8] = __builtin_amdgcn_s_memtime() - sv0;
             P.st->dbg[9] = __builtin_amdgcn_s_memrealtime() - sr0;
         }
 #ifndef LO_PKO_SUMS_COUNTERS
-        {                                    // every candidate's solve: the largest (dbg[16]), the sum and count
+        if (tid == 0) {                      // every candidate's solve: the largest (dbg[16]), the sum and count
             const float keep = pn[1] + delta[1];   // (dbg[17] / [18], cumulative) in shader cycles
             asm volatile("" :: "v"(keep));
             const unsigned long long cyc = __builtin_amdgcn_s_memtime() - sv0;
@@ -914,29 +913,19 @@ __device__ void acc_candidate_exact(const KParams& P, double scale, int c, float
             atomicAdd(&P.st->dbg[17], cyc);
             atomicAdd(&P.st->dbg[18], 1ull);
         }
-        {                                    // the same solve again, now with its code in the instruction cache: the
-            float tot2[kExactTerms], pn2[12], delta2[6];   // largest (dbg[19]) and the sum (dbg[20]) of its cycles
+#endif
+#endif
+        if (tid == 0) {
 #pragma unroll
-            for (int k = 0; k < kExactTerms; ++k) { tot2[k] = tot[k]; asm volatile("" : "+v"(tot2[k])); }
-            const unsigned long long s2 = __builtin_amdgcn_s_memtime();
-            const bool conv2 = exact_solve_step(tot2, T, P.tol_t, P.tol_r, pn2, delta2);
-            const float keep = pn2[1] + delta2[1] + (conv2 ? 1.0f : 0.0f);
-            asm volatile("" :: "v"(keep));
-            const unsigned long long cyc = __builtin_amdgcn_s_memtime() - s2;
-            atomicMax(&P.st->dbg[19], cyc);
-            atomicAdd(&P.st->dbg[20], cyc);
+            for (int q = 0; q < 12; ++q) s_rec[q] = pn[q];
+            s_rec[kCandCost] = s_tot[42];
+            int k = 0;
+            for (int r = 0; r < 6; ++r) for (int cc = r; cc < 6; ++cc) s_rec[kCandH + k++] = s_tot[r * 6 + cc];
+#pragma unroll
+            for (int j = 0; j < 6; ++j) { s_rec[kCandG + j] = s_tot[36 + j]; s_rec[kCandD + j] = delta[j]; }
+            s_rec[kCandConv] = conv ? 1.0f : 0.0f;
+            s_rec[kCandConv + 1] = 0.0f;
         }
-#endif
-#endif
-#pragma unroll
-        for (int q = 0; q < 12; ++q) s_rec[q] = pn[q];
-        s_rec[kCandCost] = tot[42];
-        int k = 0;
-        for (int r = 0; r < 6; ++r) for (int cc = r; cc < 6; ++cc) s_rec[kCandH + k++] = tot[r * 6 + cc];
-#pragma unroll
-        for (int j = 0; j < 6; ++j) { s_rec[kCandG + j] = tot[36 + j]; s_rec[kCandD + j] = delta[j]; }
-        s_rec[kCandConv] = conv ? 1.0f : 0.0f;
-        s_rec[kCandConv + 1] = 0.0f;
     }
     __syncthreads();
     if (tid < kCandWords) P.cand_rec[static_cast<size_t>(c) * kCandWords + tid] = s_rec[tid];

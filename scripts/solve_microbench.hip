@@ -55,6 +55,57 @@ __global__ void k_bench(const float* in, float* out, unsigned long long* cyc, in
     out[0] = acc;
 }
 
+// The wave-cooperative forms (lo_exact.h exact_solve_step_wave), all 64 lanes active.  V 0: the whole solve, 1: the
+// LDLT across the wave with the one-lane pose update, 2: ldlt6_solve_wave alone, 3: so3_project_svd_wave alone;
+// 4: (one lane's cost, run by every lane alike) sincosf_ref twice, 5: mul33e
+template <int V>
+__global__ void k_bench_wave(const float* in, float* out, unsigned long long* cyc, int reps) {
+    __shared__ float tot[64];
+    const int lane = threadIdx.x;
+    tot[lane] = in[lane];
+    float pose[12];
+    for (int k = 0; k < 12; ++k) pose[k] = in[64 + k];
+    __syncthreads();
+    float acc = 0.0f;
+    const unsigned long long t0 = __builtin_amdgcn_s_memtime();
+    for (int r = 0; r < reps; ++r) {
+        float pn[12], delta[6];
+        if constexpr (V == 0) {
+            const bool c = exact_solve_step_wave(tot, pose, 1e-4, 1e-4, lane, pn, delta);
+            acc += pn[0] + pn[5] + pn[11] + (c ? 1.0f : 0.0f);
+        } else if constexpr (V == 1) {                   // the LDLT across the wave, the pose update as one lane runs it
+            ldlt6_solve_wave(tot, lane, delta);
+            const float dw[3] = {delta[3], delta[4], delta[5]};
+            float Rd[3][3], R[3][3], M[3][3], Rn[3][3];
+            so3_exp_exact(dw, Rd);
+            for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) R[a][b] = pose[a * 4 + b];
+            mul33e(R, Rd, M);
+            so3_project_svd(M, Rn);
+            acc += Rn[0][0] + Rn[1][1] + Rn[2][2] + delta[0];
+        } else if constexpr (V == 2) {
+            ldlt6_solve_wave(tot, lane, delta);
+            acc += delta[0] + delta[5];
+        } else if constexpr (V == 3) {
+            const int e = lane & 15;
+            const float m = e < 9 ? pose[(e / 3) * 4 + e % 3] * (1.0f + 1e-7f * tot[e]) : 0.0f;
+            acc += wv_get(so3_project_svd_wave(m, lane), 0);
+        } else if constexpr (V == 4) {
+            const float th = 0.01f + tot[36] * 1e-3f;
+            acc += sincosf_ref(th, 0) + sincosf_ref(th, 1);
+        } else {
+            float A[3][3], B[3][3], C[3][3];
+            for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) { A[a][b] = pose[a * 4 + b]; B[a][b] = tot[a * 3 + b]; }
+            mul33e(A, B, C);
+            acc += C[0][0] + C[1][2] + C[2][1];
+        }
+        __syncthreads();
+        if (lane == 0) tot[r % kExactTerms] += acc * 1e-30f;   // chain the next call on this one
+        __syncthreads();
+    }
+    const unsigned long long t1 = __builtin_amdgcn_s_memtime();
+    if (lane == 0) { cyc[0] = t1 - t0; out[0] = acc; }
+}
+
 int main() {
     float h_in[128] = {};
     std::srand(3);
@@ -94,6 +145,24 @@ int main() {
         CK(hipMemcpy(&cyc, d_c, 8, hipMemcpyDeviceToHost));
         if (v < 4) std::printf("%-28s %8.0f cycles per call\n", names[v], static_cast<double>(cyc) / reps);
         else std::printf("%-28s %8.1f cycles per dependent op\n", names[v], static_cast<double>(cyc) / reps / 128.0);
+    }
+    const char* wnames[] = {"exact_solve_step_wave", "  LDLT across the wave only", "ldlt6_solve_wave", "so3_project_svd_wave",
+                            "2 x sincosf_ref (one lane)", "mul33e (one lane)"};
+    for (int v = 0; v < 6; ++v) {
+        for (int w = 0; w < 2; ++w) {
+            switch (v) {
+                case 0: hipLaunchKernelGGL(k_bench_wave<0>, dim3(1), dim3(64), 0, 0, d_in, d_out, d_c, reps); break;
+                case 1: hipLaunchKernelGGL(k_bench_wave<1>, dim3(1), dim3(64), 0, 0, d_in, d_out, d_c, reps); break;
+                case 2: hipLaunchKernelGGL(k_bench_wave<2>, dim3(1), dim3(64), 0, 0, d_in, d_out, d_c, reps); break;
+                case 3: hipLaunchKernelGGL(k_bench_wave<3>, dim3(1), dim3(64), 0, 0, d_in, d_out, d_c, reps); break;
+                case 4: hipLaunchKernelGGL(k_bench_wave<4>, dim3(1), dim3(64), 0, 0, d_in, d_out, d_c, reps); break;
+                default: hipLaunchKernelGGL(k_bench_wave<5>, dim3(1), dim3(64), 0, 0, d_in, d_out, d_c, reps); break;
+            }
+            CK(hipDeviceSynchronize());
+        }
+        unsigned long long cyc = 0;
+        CK(hipMemcpy(&cyc, d_c, 8, hipMemcpyDeviceToHost));
+        std::printf("%-28s %8.0f cycles per call\n", wnames[v], static_cast<double>(cyc) / reps);
     }
     // one call per launch: the instruction cache as a candidate workgroup meets the solve (once per PKO launch)
     for (int w = 0; w < 4; ++w) {
