@@ -155,7 +155,7 @@ int lo_icp_result(lo_ctx* ctx, float T_out[12], lo_iter_log* logs, lo_stats* sta
 /* stats->gpu_ms: the device time of a synchronous call (HIP events around its launches); -1 after an async call,
  * which records no events (each marker packet costs several us of device time between two kernels). */
 int lo_sync(lo_ctx* ctx);
-void* lo_stream(lo_ctx* ctx);   /* hipStream_t of the context */
+void* lo_stream(lo_ctx* ctx);   /* hipStream_t of the context (enqueues a pending hold first, as lo_icp_flush) */
 /* Run the context on a caller stream (e.g. the framework's current stream); NULL = own stream again (a fresh
  * hipStreamNonBlocking stream -- so the legacy default stream, handle 0, cannot be selected: pass a created stream). */
 int lo_set_stream(lo_ctx* ctx, void* hip_stream);
@@ -176,12 +176,41 @@ int lo_set_exact(lo_ctx* ctx, int enable);
 /* Scan pipeline (default on; LO_PIPE=0 in the environment turns it off at lo_create).  The reference's optimize
  * runs GN iterations until convergence (IterativeClosestPointOptimizer.cpp:281-449); the device loop enqueues all
  * max_iterations and a converged scan's later launches leave early.  With the pipeline, iterations >= main_iterations
- * (default 2) of a small surfel scan with PKO go to a second stream of the context, and the context stream waits on
+ * (default 2; 1 for a queued scan whose head overlapped the previous scan, below) of a small surfel scan with PKO go to a second stream of the context, and the context stream waits on
  * the device only until the scan's result is final: the early-exit launches of a converged scan drain beside the
- * next scan instead of in front of it.  Results are identical with the pipeline on or off; everything enqueued on
- * the context stream after an optimize sees its final result; lo_sync drains both streams.  main_iterations 0 keeps
- * the current split. */
+ * next scan instead of in front of it.  Results are identical with the pipeline on or off; everything enqueued
+ * THROUGH THE LIBRARY after an optimize, or on the context stream after lo_icp_flush, sees its final result (scan
+ * overlap, below); lo_sync drains both streams.  main_iterations 0 keeps the current split. */
 int lo_set_pipeline(lo_ctx* ctx, int enable, int main_iterations);
+/* Scan overlap (default on; LO_OVERLAP=0 in the environment turns it off at lo_create).  A pipelined scan's hold of
+ * the context stream is not enqueued with the scan: the next lo_icp_optimize_async of such a scan enqueues its own
+ * first correspondence launch and exact scale first -- they depend on that scan's points, its T_init and the map, not
+ * on the running scan -- then the hold, then its PKO launches, so that head runs beside the previous scan's tail on a
+ * second set of per-scan state.
+ * WHO GAINS: only a caller that enqueues scan k + 1 with NO library call on the context since scan k.  Every other
+ * call -- lo_icp_result, lo_icp_export_pose, lo_stream, a map call, a setter -- enqueues the pending hold first, so a
+ * caller that reads or exports each scan's result before the next enqueue gets no overlap and runs exactly as with
+ * overlap off (same launches, same split).  A scan's record cannot be taken later either: only the last queued scan's
+ * state is readable.  So this is throughput for a stream of scans with initial poses known up front of which only the
+ * last result (or none: warm-up, a rate measurement) is read per queue; a caller that needs every pose -- relocalisation
+ * candidates, re-registration, scan-parallel ranks that gather each pose -- gains nothing today, and neither does a
+ * frame loop whose T_init comes from the previous pose.  The time from a scan's first launch to its result does not
+ * change.  Results are identical with overlap on or off.
+ * CHANGED CONTRACT (default on): two rules that did not exist before this switch --
+ *  - work a caller enqueues on a shared stream ITSELF after lo_icp_optimize_async is ordered after the scan's final
+ *    result only once lo_icp_flush (or any other library call on the context) has been made;
+ *  - the tail of a scan reads its points while the next scan's head runs: the device buffers of the LAST TWO queued
+ *    scans must stay valid and unchanged until lo_icp_result (or lo_sync) has returned.  Code that reused or freed a
+ *    scan's buffer in stream order right after lo_icp_optimize_async (a tensor handed back to a caching allocator) must
+ *    call lo_icp_flush first, or switch the overlap off.
+ * NOTE lo_stream: it is a getter that may launch the pending hold (whoever asks for the stream is about to enqueue on
+ * it; the device map, the loop detector and the map builder take it this way); poll the handle once, not in a loop.
+ * lo_scan_overlap_status: out[0] enabled, out[1] scans whose head was enqueued in front of the previous scan's hold. */
+int lo_set_scan_overlap(lo_ctx* ctx, int enable);
+int lo_scan_overlap_status(lo_ctx* ctx, long long out[2]);
+/* Enqueue the pending hold of the last queued scan on the context stream now (no-op when there is none): what follows
+ * on that stream sees the scan's final result.  Does not wait on the host. */
+int lo_icp_flush(lo_ctx* ctx);
 /* IterativeClosestPointOptimizer::update_config (IterativeClosestPointOptimizer.h:220): new parameters, same context --
  * the device map, buffers and stream stay.  voxel_size, hierarchy_factor, max_points and use_surfel_correspondence
  * are fixed at lo_create (LO_ERR_STATE); new PKO parameters rebuild the PKO tables. */
@@ -196,8 +225,9 @@ int lo_set_pko_groups(lo_ctx* ctx, int groups);
  * record of an async scan); lo_icp_result re-runs it on one stream instead of returning that status.  That re-run reads
  * the points of the context's LAST enqueued scan again: after lo_icp_optimize_async / lo_icp_optimize_raw_async the
  * caller's device buffer (d_pts / d_raw, and the device count) must therefore stay valid and unchanged until
- * lo_icp_result has returned -- the same lifetime a stream-ordered reader of the buffer needs anyway.  Earlier async
- * scans are never re-run: their exported records keep LO_ERR_PIPELINE. */
+ * lo_icp_result has returned -- the same lifetime a stream-ordered reader of the buffer needs anyway (with scan
+ * overlap, the last TWO queued scans' buffers: see lo_set_scan_overlap).  Earlier async scans are never re-run: their
+ * exported records keep LO_ERR_PIPELINE. */
 int lo_pipeline_status(lo_ctx* ctx, int out[4]);
 /* In-step timing: with enable, each optimize brackets its FIRST correspondence launch (k_correspond, or the KDTree
  * k_knn + k_knn_brute + k_plane) with HIP events on the context stream (up to 1024 scans; enabling resets them).
@@ -408,6 +438,10 @@ int lo_exact_solve_both(lo_ctx* ctx, const float* totals, const float* poses, si
  * by lo_update_config); an allocated buffer that no launch has written yet holds undefined words, so a caller matches
  * the records against a logged GN step instead of reading them as such.  LO_ERR_CAPACITY when cap_words is too small. */
 int lo_debug_cand_records(lo_ctx* ctx, float* out, size_t cap_words);
+/* Diagnostic (scan overlap): drains both streams, then the 16-float record, laid out as lo_icp_export_pose's, of the
+ * scan on the other set of per-scan state -- the scan queued before the last one, whose tail ran beside the last
+ * scan's head.  LO_ERR_STATE until a scan has overlapped on this context. */
+int lo_debug_other_lane_record(lo_ctx* ctx, float out16[16]);
 /* Diagnostic: 16 device counters (phase timestamps of the -DLO_PKO_STAMPS build; zeros otherwise). */
 int lo_debug_counters(lo_ctx* ctx, unsigned long long out[16]);
 /* Diagnostic: the first n (<= 24) device counters. */

@@ -92,6 +92,7 @@ struct lo_batch {
 
 namespace lo {
 BatchView batch_view(lo_batch* b) {
+    for (lo_ctx* c : b->ctx) (void)flush_hold(c);      // (the map update that asks is about to change what scans read)
     return BatchView{b->ctx.data(), static_cast<int>(b->ctx.size()), b->device, b->stream, b->pending, b->kd};
 }
 void batch_set_error(lo_batch* b, const char* msg) { b->err = msg; }
@@ -161,6 +162,9 @@ static int batch_filter(lo_batch* b, const float* const* raw, const size_t* n_ra
         }
     }
     LO_HIP(b, hipSetDevice(b->device));
+    for (lo_ctx* c : b->ctx) {                         // a queued single scan's pending hold first (scan overlap)
+        if (flush_hold(c) != LO_OK) { b->err = c->err; return LO_ERR_HIP; }
+    }
     size_t max_m = 0;
     for (int j = 0; j < B; ++j) {
         lo_ctx* c = b->ctx[j];
@@ -286,6 +290,9 @@ int lo_batch_optimize_async(lo_batch* b, const float* const* d_pts, const size_t
         }
     }
     LO_HIP(b, hipSetDevice(b->device));
+    for (lo_ctx* c : b->ctx) {                         // a queued single scan's pending hold first (scan overlap)
+        if (flush_hold(c) != LO_OK) { b->err = c->err; return LO_ERR_HIP; }
+    }
     for (int j = 0; j < B; ++j) {                      // PKO / candidate buffers first (their pointers go into the params)
         if (n[j] == 0) continue;
         const int rc = ensure_acc_part(b->ctx[j]);
@@ -506,6 +513,9 @@ int lo_batch_optimize(lo_batch* b, const float* const* pts, const size_t* n, con
     if (b->pending) { b->err = "batch in flight: call lo_batch_result first"; return LO_ERR_STATE; }
     const int B = static_cast<int>(b->ctx.size());
     LO_HIP(b, hipSetDevice(b->device));
+    for (lo_ctx* c : b->ctx) {                         // a queued single scan's pending hold first (scan overlap)
+        if (flush_hold(c) != LO_OK) { b->err = c->err; return LO_ERR_HIP; }
+    }
     for (int j = 0; j < B; ++j) {
         if (n[j] == 0) continue;
         if (!pts[j]) return LO_ERR_ARG;

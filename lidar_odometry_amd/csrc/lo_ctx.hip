@@ -9,6 +9,7 @@
 namespace lo {
 // Both streams of the context drained (lo_sync, lo_set_stream, lo_destroy).
 hipError_t sync_all(lo_ctx* c) {
+    if (c->stream && flush_hold(c) != LO_OK) return hipErrorUnknown;   // (the text is in c->err)
     hipError_t e = c->stream ? hipStreamSynchronize(c->stream) : hipSuccess;
     if (e == hipSuccess && c->s_tail) e = hipStreamSynchronize(c->s_tail);
     return e;
@@ -81,7 +82,11 @@ int lo_get_config(const lo_ctx* ctx, lo_config* out) {
     return LO_OK;
 }
 int lo_device(const lo_ctx* ctx) { return ctx ? ctx->device : -1; }
-void* lo_stream(lo_ctx* ctx) { return ctx ? static_cast<void*>(ctx->stream) : nullptr; }
+// (whoever asks for the stream is about to enqueue on it: a pending hold goes first)
+void* lo_stream(lo_ctx* ctx) {
+    if (ctx) (void)flush_hold(ctx);
+    return ctx ? static_cast<void*>(ctx->stream) : nullptr;
+}
 
 }  // extern "C"
 
@@ -209,7 +214,8 @@ lo_ctx* lo_create(const lo_config* cfg, int device, int* err) {
         if (*cc && std::strcmp(cc, "0") != 0 && std::strcmp(cc, "False") != 0 && std::strcmp(cc, "false") != 0) c->pipe = false;
     }
     if (const char* pp = std::getenv("LO_PIPE")) c->pipe = std::atoi(pp) != 0;
-    if (const char* pm = std::getenv("LO_PIPE_MAIN")) c->pipe_main = std::max(1, std::atoi(pm));
+    if (const char* pm = std::getenv("LO_PIPE_MAIN")) { c->pipe_main = std::max(1, std::atoi(pm)); c->pipe_main_auto = false; }
+    if (const char* po = std::getenv("LO_OVERLAP")) c->overlap = std::atoi(po) != 0;
     if (const char* pw = std::getenv("LO_PIPE_WAIT_MS")) c->pipe_bound = 100000ull * std::max(1, std::atoi(pw));
     if (const char* pf = std::getenv("LO_PIPE_FAIL_AT")) c->pipe_fail_at = static_cast<uint32_t>(std::max(0, std::atoi(pf)));
     if (const char* pg = std::getenv("LO_PKO_GROUPS")) c->pko_groups = std::max(0, std::atoi(pg));
@@ -276,22 +282,28 @@ int lo_update_config(lo_ctx* c, const lo_config* cfg) {
     c->cfg = *cfg;
     ++c->cfg_gen;                                        // batches re-upload this context's parameters
     if (na_changed || (cfg->use_adaptive_m_estimator && !c->d_acc_part)) {
-        // the candidate buffers are sized by the alpha grid: re-made on the next optimize
+        // the candidate buffers are sized by the alpha grid: re-made on the next optimize (the second lane whole)
         c->d_acc_part.reset();
         c->d_cand_rec.reset();
         c->d_cand_cnt.reset();
+        c->alt = lo_ctx::ScanLane{};
+        c->alt_ready = false;
     }
     return LO_OK;
 }
 
 int lo_set_exact(lo_ctx* c, int enable) {
     if (!c) return LO_ERR_ARG;
+    const int rc = flush_hold(c);
+    if (rc != LO_OK) return rc;
     c->exact = enable != 0;
     return LO_OK;
 }
 
 int lo_set_pko_groups(lo_ctx* c, int groups) {
     if (!c || groups < 0) return LO_ERR_ARG;
+    const int rc = flush_hold(c);
+    if (rc != LO_OK) return rc;
     c->pko_groups = groups;
     return LO_OK;
 }
@@ -307,8 +319,25 @@ int lo_pipeline_status(lo_ctx* c, int out[4]) {
 
 int lo_set_pipeline(lo_ctx* c, int enable, int main_iterations) {
     if (!c || main_iterations < 0) return LO_ERR_ARG;
+    const int rc = flush_hold(c);
+    if (rc != LO_OK) return rc;
     c->pipe = enable != 0;
-    if (main_iterations > 0) c->pipe_main = main_iterations;
+    if (main_iterations > 0) { c->pipe_main = main_iterations; c->pipe_main_auto = false; }
+    return LO_OK;
+}
+
+int lo_set_scan_overlap(lo_ctx* c, int enable) {
+    if (!c) return LO_ERR_ARG;
+    const int rc = flush_hold(c);
+    if (rc != LO_OK) return rc;
+    c->overlap = enable != 0;
+    return LO_OK;
+}
+
+int lo_scan_overlap_status(lo_ctx* c, long long out[2]) {
+    if (!c || !out) return LO_ERR_ARG;
+    out[0] = c->overlap ? 1 : 0;
+    out[1] = static_cast<long long>(c->overlapped);
     return LO_OK;
 }
 
@@ -324,6 +353,8 @@ int lo_set_stream(lo_ctx* c, void* stream) {
 
 int lo_icp_export_pose(lo_ctx* c, float* d_out16) {
     if (!c || !d_out16) return LO_ERR_ARG;
+    const int rc = flush_hold(c);
+    if (rc != LO_OK) return rc;
     hipLaunchKernelGGL(k_export_pose, dim3(1), dim3(64), 0, c->stream, c->d_st, d_out16);
     LO_HIP(c, hipGetLastError());
     return LO_OK;

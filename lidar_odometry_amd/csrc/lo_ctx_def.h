@@ -169,7 +169,10 @@ struct lo_ctx {
     // part is done (k_wait_seq polls the word the main part's last pick sets); no HIP events on the hot path (every
     // marker packet costs ~5-7 us of device time between two kernels).
     bool pipe = true;
-    int pipe_main = 2;
+    int pipe_main = 1;              // (1: the tail then carries ~1.4 working iterations per scan, and the whole head of
+                                    //   the next scan hides under it)
+    bool pipe_main_auto = true;     // no split chosen (lo_set_pipeline / LO_PIPE_MAIN): only a scan whose own head overlapped
+                                    //   takes pipe_main, every other scan keeps the split 2 it always had -- 1 costs it ~1 %
     int pko_groups = 0;             // EM workgroups per PKO launch (lo_set_pko_groups / LO_PKO_GROUPS; 0 = one per alpha)
     bool pko_solo = false;          // LO_PKO_SOLO=1 (A/B): the speculative PKO launch asks for enough LDS that one
                                     //   workgroup holds a CU alone (no other launch's waves on its SIMDs)
@@ -183,6 +186,32 @@ struct lo_ctx {
     uint32_t pipe_fail_at = 0;      // test hook (LO_PIPE_FAIL_AT=k): the k-th pipelined scan's tail wait gives up at once
     unsigned pipe_timeouts = 0;     // times a wait timed out and the pipeline was switched off (lo_pipeline_status)
     unsigned pipe_reruns = 0;       // synchronous scans re-run on one stream after such a timeout
+    // scan overlap (lo_set_scan_overlap; on by default, LO_OVERLAP=0): a pipelined scan does not end with its
+    // k_wait_final -- the hold is kept pending (hold_seq, hold_st) and enqueued by the next pipelined scan after that
+    // scan's own head (first correspondence launch + exact scale), which therefore runs beside this scan's tail.  The
+    // head writes the per-scan state the tail still reads, so the context owns two sets of it ("lanes"): the members
+    // above are the lane of the last enqueued scan, `alt` is the other one (allocated the first time a scan is enqueued
+    // while another is in flight), and lane_switch swaps them.  Every other entry point that touches the context stream
+    // or a queued scan's inputs enqueues the pending hold first (flush_hold), after which the context is as it was
+    // before this existed.  The map, the PKO tables and the d_fin words are shared.
+    struct ScanLane {
+        DevBuf<int32_t> d_slot;
+        DevBuf<double> d_res_pko;
+        DevBuf<uint64_t> d_wmask;
+        DevBuf<int32_t> d_blk_cnt;
+        DevBuf<double> d_blk_sum, d_blk_m2, d_blk_part, d_acc_part;
+        DevBuf<float> d_cand_rec;
+        DevBuf<unsigned> d_cand_cnt;
+        DevBuf<double> d_js;
+        DevBuf<DevState> d_st;
+    };
+    ScanLane alt;
+    bool alt_ready = false;         // alt holds a full set, its candidate buffers sized for the current alpha grid
+    int lane = 0;                   // which set the members above are (scan k of an overlapped run: k & 1)
+    bool overlap = true;
+    uint32_t hold_seq = 0;          // the scan whose k_wait_final is still to be enqueued (0: none)
+    DevState* hold_st = nullptr;    //   and its lane's DevState (a timed-out wait marks it LO_ERR_PIPELINE)
+    unsigned long long overlapped = 0;   // scans whose head was enqueued in front of the previous scan's hold
     const float* last_pts = nullptr;   // the scan in flight (a re-run after a pipeline timeout)
     const int* last_ndev = nullptr;
     bool sync_call = false;         // the optimize in flight is a synchronous call: HIP events time it (gpu_ms)
@@ -213,6 +242,7 @@ void launch_pko_spec(lo_ctx* c, const KParams& P, int it, hipStream_t s = nullpt
 void launch_brute(lo_ctx* c, const KParams& P);
 void launch_correspond(lo_ctx* c, const KParams& P, int with_stats, bool kd);
 int enqueue_optimize(lo_ctx* c, const float* d_pts, size_t n, const float T_init[12], const int* n_dev = nullptr);
+int flush_hold(lo_ctx* c);     // the pending hold of the last pipelined scan, enqueued on the context stream now
 
 // ---- per-scan helpers on the launch path of every optimize, single and batched: inline, as when one file held them
 // PKO workgroups: one alpha of the JS grid per workgroup (each fits the GMM redundantly), capped at kPkoMaxWGs

@@ -358,6 +358,7 @@ int loop_map_from_device(lo_ctx* c, PointGrid& G, const float* d_xyz, size_t m, 
 
 int ctx_grid_from_device(lo_ctx* c, const float* d_xyz, const int* d_count, size_t cap) {
     if (!c || !d_xyz || !d_count) return LO_ERR_ARG;
+    { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
     if (!c->kd) { c->err = "ctx_grid_from_device: a KDTree-mode context"; return LO_ERR_STATE; }
     LO_HIP(c, hipSetDevice(c->device));
     const int rc = grid_from_device(c, c->grid, d_xyz, d_count, cap, 0);
@@ -661,6 +662,7 @@ extern "C" {
 
 int lo_map_set_points(lo_ctx* c, const float* xyz, size_t m) {
     if (!c) return LO_ERR_ARG;
+    { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
     if (!c->kd) { c->err = "lo_map_set_points needs use_surfel_correspondence = 0"; return LO_ERR_STATE; }
     c->grid_dev = false;
     return grid_build(c, c->grid, xyz, m);

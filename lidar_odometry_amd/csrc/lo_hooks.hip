@@ -67,6 +67,7 @@ static int reset_state(lo_ctx* c, const float T[12], double scale, double alpha)
 
 int lo_find_correspondences(lo_ctx* c, const float* pts, size_t n, const float T[12], uint8_t* valid, double* residual) {
     if (!c || !T || (n > 0 && (!pts || !valid || !residual))) return LO_ERR_ARG;
+    { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
     if (n > static_cast<size_t>(c->cfg.max_points)) { c->err = "n exceeds max_points"; return LO_ERR_CAPACITY; }
     if (n == 0) return 0;
     LO_HIP(c, hipSetDevice(c->device));
@@ -90,6 +91,7 @@ int lo_find_correspondences(lo_ctx* c, const float* pts, size_t n, const float T
 
 int lo_knn_search(lo_ctx* c, const float* q, size_t n, int32_t* idx, float* dist) {
     if (!c || (n > 0 && (!q || !idx || !dist))) return LO_ERR_ARG;
+    { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
     if (!c->kd) { c->err = "lo_knn_search needs use_surfel_correspondence = 0"; return LO_ERR_STATE; }
     if (n > static_cast<size_t>(c->cfg.max_points)) { c->err = "n exceeds max_points"; return LO_ERR_CAPACITY; }
     if (n == 0) return 0;
@@ -130,6 +132,7 @@ int lo_knn_search(lo_ctx* c, const float* q, size_t n, int32_t* idx, float* dist
 
 double lo_pko_scale_factor(lo_ctx* c, const double* residuals, size_t n, double* gmm_out) {
     if (!c || (n > 0 && !residuals)) return NAN;
+    if (flush_hold(c) != LO_OK) return NAN;
     if (n == 0) return 1.0;                                  // calculate_scale_factor, empty input (:66-69)
     if (n > static_cast<size_t>(c->cfg.max_points)) { c->err = "n exceeds max_points"; return NAN; }
     if (hipSetDevice(c->device) != hipSuccess) return NAN;
@@ -152,6 +155,7 @@ double lo_pko_scale_factor(lo_ctx* c, const double* residuals, size_t n, double*
 int lo_build_normal_equations(lo_ctx* c, const float* pts, size_t n, const float T[12], double scale, double delta,
                               double H[36], double g[6], double* cost) {
     if (!c || !T || !H || !g || !cost || (n > 0 && !pts)) return LO_ERR_ARG;
+    { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
     if (n > static_cast<size_t>(c->cfg.max_points)) { c->err = "n exceeds max_points"; return LO_ERR_CAPACITY; }
     if (n == 0) { std::memset(H, 0, 36 * sizeof(double)); std::memset(g, 0, 6 * sizeof(double)); *cost = 0; return 0; }
     LO_HIP(c, hipSetDevice(c->device));
@@ -210,6 +214,7 @@ static unsigned long long span_of(const unsigned long long* r) {
 
 int lo_set_stage_timing(lo_ctx* c, int enable) {
     if (!c) return LO_ERR_ARG;
+    { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
     if (enable && c->st_ev.empty()) {
         c->st_ev.resize(2 * kStageEvents, nullptr);
         for (hipEvent_t& e : c->st_ev) LO_HIP(c, hipEventCreate(&e));
@@ -226,6 +231,7 @@ int lo_set_stage_timing(lo_ctx* c, int enable) {
 
 int lo_stage_span(lo_ctx* c, double* avg_us, int* count) {
     if (!c || !avg_us) return LO_ERR_ARG;
+    { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
     *avg_us = 0.0;
     if (count) *count = 0;
     if (!c->d_span || c->st_n == 0) return LO_OK;
@@ -246,6 +252,7 @@ int lo_stage_span(lo_ctx* c, double* avg_us, int* count) {
 
 int lo_stage_time(lo_ctx* c, double* avg_us, int* count) {
     if (!c || !avg_us) return LO_ERR_ARG;
+    { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
     LO_HIP(c, hipStreamSynchronize(c->stream));
     double tot = 0.0;
     for (int i = 0; i < c->st_n; ++i) {
@@ -272,6 +279,7 @@ int lo_pko_em_stats(lo_ctx* c, unsigned long long out[3], int reset) {
 int lo_bench_kernel(lo_ctx* c, const float* d_pts, size_t n, const float T[12], double scale, double alpha,
                     int kernel_id, int reps, float* avg_ms) {
     if (!c || !d_pts || !T || !avg_ms || n == 0 || reps < 1 || kernel_id < 0 || kernel_id > 5) return LO_ERR_ARG;
+    { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
     if (kernel_id == 5 && c->kd) { c->err = "kernel 5: surfel correspondence only"; return LO_ERR_STATE; }
     if (n > static_cast<size_t>(c->cfg.max_points)) { c->err = "n exceeds max_points"; return LO_ERR_CAPACITY; }
     LO_HIP(c, hipSetDevice(c->device));
@@ -328,6 +336,7 @@ int lo_bench_correspond_rr(lo_ctx* const* ctxs, const float* const* d_pts, const
     for (int i = 0; i < count; ++i) {
         lo_ctx* c = ctxs[i];
         if (!c || !d_pts[i] || n[i] == 0) return LO_ERR_ARG;
+        if (flush_hold(c) != LO_OK) { c0->err = c->err; return LO_ERR_HIP; }
         if (c->kd || c->device != c0->device) { c0->err = "lo_bench_correspond_rr: surfel contexts on one device"; return LO_ERR_STATE; }
         if (n[i] > static_cast<size_t>(c->cfg.max_points)) { c0->err = "n exceeds max_points"; return LO_ERR_CAPACITY; }
     }
@@ -355,6 +364,7 @@ int lo_bench_correspond_rr(lo_ctx* const* ctxs, const float* const* d_pts, const
 
 int lo_seq_sum_f64(lo_ctx* c, const double* x, size_t n, int sort, double* out_sum, long long stats[4]) {
     if (!c || !out_sum || (n > 0 && !x) || n > static_cast<size_t>(kExactMaxPoints)) return LO_ERR_ARG;
+    { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
     LO_HIP(c, hipSetDevice(c->device));
     DevBuf<double> buf;
     static_assert(sizeof(long long) == sizeof(double), "the four stats words follow the doubles");
@@ -374,6 +384,7 @@ int lo_seq_sum_f64(lo_ctx* c, const double* x, size_t n, int sort, double* out_s
 
 int lo_seq_sum_f32(lo_ctx* c, const float* x, size_t n, float* out_sum, long long stats[4]) {
     if (!c || !out_sum || (n > 0 && !x) || n > static_cast<size_t>(kMaxBlocks) * kBlock) return LO_ERR_ARG;
+    { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
     LO_HIP(c, hipSetDevice(c->device));
     const int ni = static_cast<int>(n);
     const size_t x_bytes = (n * sizeof(float) + 255) / 256 * 256, mwb = mw_bytes(1, ni);
@@ -414,6 +425,7 @@ int lo_seq_sum_f32(lo_ctx* c, const float* x, size_t n, float* out_sum, long lon
 int lo_exact_solve_both(lo_ctx* c, const float* totals, const float* poses, size_t n, double tol_t, double tol_r,
                         uint32_t* out_lane, uint32_t* out_wave) {
     if (!c || n == 0 || n > (1u << 20) || !totals || !poses || !out_lane || !out_wave) return LO_ERR_ARG;
+    { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
     LO_HIP(c, hipSetDevice(c->device));
     const size_t tb = n * kExactTerms * sizeof(float), pb = n * 12 * sizeof(float), ob = n * kSolveWords * sizeof(uint32_t);
     DevBuf<char> buf;
@@ -438,12 +450,31 @@ int lo_exact_solve_both(lo_ctx* c, const float* totals, const float* poses, size
 
 int lo_debug_cand_records(lo_ctx* c, float* out, size_t cap_words) {
     if (!c || !out) return LO_ERR_ARG;
+    { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
     const size_t cand = static_cast<size_t>(c->cfg.num_alpha_segments) + 1, words = cand * kCandWords;
     if (!c->d_acc_part || c->d_cand_rec.capacity() < words) { c->err = "lo_debug_cand_records: no records yet"; return LO_ERR_STATE; }
     if (cap_words < words) { c->err = "lo_debug_cand_records: output too small"; return LO_ERR_CAPACITY; }
     LO_HIP(c, sync_all(c));
     LO_HIP(c, hipMemcpy(out, c->d_cand_rec, words * sizeof(float), hipMemcpyDeviceToHost));
     return static_cast<int>(cand);
+}
+
+// The 16-float record (as lo_icp_export_pose) of the scan on the OTHER lane: the scan queued before the last one, whose
+// tail ran beside the last scan's head (scan overlap).  Drains both streams first.
+int lo_debug_other_lane_record(lo_ctx* c, float out16[16]) {
+    if (!c || !out16) return LO_ERR_ARG;
+    LO_HIP(c, hipSetDevice(c->device));
+    LO_HIP(c, sync_all(c));
+    if (!c->alt_ready) { c->err = "lo_debug_other_lane_record: no scan has overlapped yet"; return LO_ERR_STATE; }
+    std::vector<char> h(offsetof(DevState, logs));
+    LO_HIP(c, hipMemcpy(h.data(), c->alt.d_st.get(), h.size(), hipMemcpyDeviceToHost));
+    const DevState* st = reinterpret_cast<const DevState*>(h.data());   // (header fields only)
+    for (int k = 0; k < 12; ++k) out16[k] = st->pose[k];
+    out16[12] = static_cast<float>(st->status);
+    out16[13] = static_cast<float>(st->iter);
+    out16[14] = static_cast<float>(st->n_corr);
+    out16[15] = 0.0f;
+    return LO_OK;
 }
 
 int lo_debug_counters(lo_ctx* c, unsigned long long out[16]) {

@@ -69,7 +69,7 @@ static int pipe_alloc(lo_ctx* c) {
 // the pipeline off for this context, clear the flag words.  Scans enqueued before this point report LO_ERR_PIPELINE
 // (their tails left without touching anything); a synchronous call re-runs its scan on one stream (lo_icp_result).
 static int pipe_recover(lo_ctx* c) {
-    LO_HIP(c, sync_all(c));
+    LO_HIP(c, sync_all(c));                         // (enqueues a pending hold of either lane first: it gives up at once)
     c->pipe = false;
     ++c->pipe_timeouts;
     c->err = "scan pipeline: a device-side wait timed out (the two streams were not run concurrently, e.g. rocprofv3 "
@@ -80,6 +80,79 @@ static int pipe_recover(lo_ctx* c) {
     return LO_OK;
 }
 static bool pipe_flagged(const lo_ctx* c) { return c->h_broken && __atomic_load_n(c->h_broken.get(), __ATOMIC_ACQUIRE) != 0u; }
+
+// Scan overlap: the one place a pending hold leaves the host.  Called at the top of every entry point that enqueues on
+// the context stream, reads from it, or changes what a queued scan reads (and by sync_all); enqueue_optimize calls it
+// after the next scan's head instead.  The wait is k_wait_final's as before: bounded by pipe_bound, it gives up at once
+// when the pipeline is broken, and a timeout marks the held scan's own DevState (its lane's) LO_ERR_PIPELINE.
+int flush_hold(lo_ctx* c) {
+    if (c->hold_seq == 0) return LO_OK;
+    const uint32_t seq = c->hold_seq;
+    DevState* st = c->hold_st;
+    c->hold_seq = 0;
+    c->hold_st = nullptr;
+    LO_HIP(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_wait_final, dim3(1), dim3(kWave), 0, c->stream, c->d_fin, seq, st, c->d_hbroken, c->pipe_bound);
+    LO_HIP(c, hipGetLastError());
+    return LO_OK;
+}
+
+// A small scan whose PKO launches pre-solve the candidates (k_pick* selects one): the launch sequence of the fast mode,
+// in reference-exact mode with the one-workgroup sort.  enqueue_optimize computes this once, before the lanes are
+// chosen, and every branch below tests it; the KParams it is later built into must agree (checked there).
+static bool cand_scan(const lo_ctx* c, size_t n) {
+    const lo_config& g = c->cfg;
+    const size_t nb = (n + kBlock - 1) / kBlock;          // nb_acc = min(nb, kAccBlocks) <= kFuseMaxBlocks
+    return n > 0 && g.use_adaptive_m_estimator && c->presolve && nb <= static_cast<size_t>(kFuseMaxBlocks) &&
+           g.max_iterations <= LO_MAX_ITERS && (!c->exact || n <= static_cast<size_t>(kExactMaxPoints));
+}
+// ... that goes down the scan pipeline with the split pipe_main: the only path whose head may overlap the previous
+// scan's tail
+static bool pipelined_scan(const lo_ctx* c, bool cand, int pipe_main) {
+    return cand && !c->kd && c->pipe && c->cfg.max_iterations > pipe_main;
+}
+
+// The second lane: a full set of the per-scan state (same sizes as ctx_alloc's and ensure_acc_part's), then the swap.
+// Nothing of the lane swapped in is in flight: its last scan's hold was enqueued before the scan now pending started.
+static int lane_switch(lo_ctx* c) {
+    lo_ctx::ScanLane& A = c->alt;
+    if (!c->alt_ready) {
+        const lo_config& g = c->cfg;
+        const size_t NB = (static_cast<size_t>(g.max_points) + kBlock - 1) / kBlock;
+        const size_t cand = static_cast<size_t>(g.num_alpha_segments) + 1;
+        LO_HIP(c, A.d_slot.reserve(NB * kBlock));
+        LO_HIP(c, A.d_res_pko.reserve(NB * kBlock));
+        LO_HIP(c, A.d_wmask.reserve(NB * kWavesPerBlock));
+        LO_HIP(c, A.d_blk_cnt.reserve(NB));
+        LO_HIP(c, A.d_blk_sum.reserve(NB));
+        LO_HIP(c, A.d_blk_m2.reserve(NB));
+        LO_HIP(c, A.d_blk_part.reserve(NB * kNE));
+        LO_HIP(c, A.d_js.reserve(kMaxAlpha + 1));
+        LO_HIP(c, A.d_st.reserve(1));
+        LO_HIP(c, hipMemsetAsync(A.d_st, 0, sizeof(DevState), c->stream));
+        LO_HIP(c, A.d_cand_rec.reserve(cand * kCandWords));
+        LO_HIP(c, A.d_cand_cnt.reserve(cand));
+        // zeroed on the context stream: this scan's head follows there, and its tail starts only behind its main part
+        LO_HIP(c, hipMemsetAsync(A.d_cand_cnt, 0, cand * sizeof(unsigned), c->stream));
+        LO_HIP(c, A.d_acc_part.reserve(cand * kFuseMaxBlocks * kNE));
+        c->alt_ready = true;
+    }
+    std::swap(A.d_slot, c->d_slot);
+    std::swap(A.d_res_pko, c->d_res_pko);
+    std::swap(A.d_wmask, c->d_wmask);
+    std::swap(A.d_blk_cnt, c->d_blk_cnt);
+    std::swap(A.d_blk_sum, c->d_blk_sum);
+    std::swap(A.d_blk_m2, c->d_blk_m2);
+    std::swap(A.d_blk_part, c->d_blk_part);
+    std::swap(A.d_acc_part, c->d_acc_part);
+    std::swap(A.d_cand_rec, c->d_cand_rec);
+    std::swap(A.d_cand_cnt, c->d_cand_cnt);
+    std::swap(A.d_js, c->d_js);
+    std::swap(A.d_st, c->d_st);
+    c->lane ^= 1;
+    ++c->cfg_gen;                                       // a batch's cached device KParams name the other lane's buffers
+    return LO_OK;
+}
 
 
 // ---------------------------------------------------------------- optimize
@@ -253,6 +326,28 @@ int enqueue_optimize(lo_ctx* c, const float* d_pts, size_t n, const float T_init
     // HIP events only for synchronous calls (gpu_ms): a marker packet costs ~5-7 us of device time per scan
     const bool timed = c->sync_call;
     c->last_timed = timed;
+    // scan overlap: a hold may be deferred (and a deferred one kept past this scan's head) only between two pipelined
+    // scans that nothing times -- a synchronous call's HIP events and the stage timing bracket the whole scan -- and
+    // whose points are the caller's: a device-filtered scan sits in the context's one point buffer, which the next
+    // raw call's filter overwrites, so that call enqueues the hold first anyway
+    const bool cand = cand_scan(c, n);
+    const bool may_defer = c->overlap && !timed && !c->stage_timing && !n_dev && !pipe_flagged(c);
+    // this scan's head overlaps: a hold is pending and the scan is pipelined.  Only then does it take the queue's split
+    // (pipe_main, 1 by default): the caller is queueing scans back to back, and the next head hides under a longer tail.
+    // A scan behind a flushed hold (its caller read the previous result, or made any other call) keeps the split 2 a
+    // scan always had unless one was chosen -- split 1 without overlap costs about 1 %.
+    const bool overlaps = c->hold_seq != 0 && may_defer && pipelined_scan(c, cand, c->pipe_main);
+    const int pipe_main = (c->pipe_main_auto && !overlaps) ? 2 : c->pipe_main;
+    const bool defer = may_defer && pipelined_scan(c, cand, pipe_main);
+    if (c->hold_seq != 0) {
+        if (!overlaps) {                                  // any other path: the context as it always was
+            const int rcf = flush_hold(c);
+            if (rcf != LO_OK) return rcf;
+        } else {                                          // this scan's state goes to the other lane
+            const int rcl = lane_switch(c);
+            if (rcl != LO_OK) return rcl;
+        }
+    }
     if (timed) LO_HIP(c, hipEventRecord(c->ev0, c->stream));
     if (n == 0) {
         hipLaunchKernelGGL(k_init, dim3(1), dim3(64), 0, c->stream, c->d_st, T0, 1.0, g.robust_loss_delta);
@@ -268,13 +363,17 @@ int enqueue_optimize(lo_ctx* c, const float* d_pts, size_t n, const float T_init
         // small scan with PKO: the solve of iteration it runs fused with the correspondence search of it + 1
         // (k_solve_correspond; KDTree: k_solve_knn, then k_knn_brute + k_plane), the last solve alone (k_solve_pick)
         const bool fused = spec_ok(P) && g.max_iterations <= LO_MAX_ITERS;
+        if (cand != (fused && P.cand_rec != nullptr && (!c->exact || n <= static_cast<size_t>(kExactMaxPoints)))) {
+            c->err = "enqueue_optimize: cand_scan disagrees with the scan's parameters";
+            return LO_ERR_STATE;
+        }
         int n2 = 0;
         if (c->exact) {
             const int rc3 = exact_prepare(c, P, n, &n2);
             if (rc3 != LO_OK) return rc3;
             P0.ex_terms = P.ex_terms;
             P0.scale_given = P.scale_given;
-            if (!(fused && P.cand_rec && n2 > 0)) {
+            if (!cand) {                                  // (n2 > 0 exactly when n <= kExactMaxPoints)
                 // reference-exact GN loop without candidates (lo_exact.hip): correspondences, (iteration 0) sorted-order
                 // scale, PKO, per-point fp32 terms, sequential sums + fp32 LDLT + SVD-projected update
                 for (int it = 0; it < g.max_iterations; ++it) launch_exact_iteration(c, P, P0, it, n2, c->kd);
@@ -291,7 +390,7 @@ int enqueue_optimize(lo_ctx* c, const float* d_pts, size_t n, const float T_init
             const int rc4 = pipe_recover(c);
             if (rc4 != LO_OK) return rc4;
         }
-        if (fused && P.cand_rec && !c->kd && c->pipe && g.max_iterations > c->pipe_main) {
+        if (pipelined_scan(c, cand, pipe_main)) {         // (c->pipe as it is now: a recovery above switched it off)
             // scan pipeline: iterations < pipe_main on the context stream, the rest on the tail stream behind a
             // device-side wait for the main part; k_wait_final then holds the context stream until the scan's result
             // is final
@@ -305,28 +404,46 @@ int enqueue_optimize(lo_ctx* c, const float* d_pts, size_t n, const float T_init
             Pt.tail = 1;                                  // DevState may already be the next scan's)
             KParams Ph = P;                               // the main part's last pick signals the tail (signal_main)
             Ph.hold = 1;
-            // host submission order main -> tail -> k_wait_final: every device-side wait depends only on work
-            // submitted before it (deadlock-free even if the two streams share a hardware queue)
+            // host submission order, scan k: head(k) -> k_wait_final(k - 1) -> main(k) on the context stream, then
+            // k_wait_seq(k) -> tail(k) on the tail stream; k_wait_final(k) follows head(k + 1), or comes from flush_hold.
+            // Every device-side wait depends only on work submitted before it, on any stream: k_wait_final(k - 1) polls
+            // the word that main(k - 1) or tail(k - 1) publishes, both submitted during the previous call, and
+            // k_wait_seq(k) polls the word main(k)'s last pick sets, submitted just above it.  So the order is
+            // deadlock-free even if both streams share one hardware queue (they then simply run in this order).
+            // head(k) runs on the lane that scan k - 2 used: k_wait_final(k - 2) precedes main(k - 1) on this stream, so
+            // that scan is final, and what is left of its tail leaves on tail_gone before touching anything.
             launch_correspond_first(c, P0, false);
             if (c->exact) launch_exact_scale_any(c, P, n2, c->stream);
+            if (c->hold_seq != 0) {                       // the previous scan's hold, now behind this scan's head
+                const int rcf = flush_hold(c);
+                if (rcf != LO_OK) return rcf;
+                ++c->overlapped;
+            }
             for (int it = 0; it < g.max_iterations; ++it) {
-                const bool tail = it >= c->pipe_main;
-                if (it == c->pipe_main)                   // bound 0: the test hook's forced timeout
+                const bool tail = it >= pipe_main;
+                if (it == pipe_main)                   // bound 0: the test hook's forced timeout
                     hipLaunchKernelGGL(k_wait_seq, dim3(1), dim3(kWave), 0, c->s_tail, c->d_fin, seq, c->d_st, c->d_hbroken,
                                        (c->pipe_fail_at != 0 && seq == c->pipe_fail_at) ? 0ull : c->pipe_bound);
                 const hipStream_t s = tail ? c->s_tail : c->stream;
-                const KParams& Pi = tail ? Pt : (it + 1 == c->pipe_main ? Ph : P);
+                const KParams& Pi = tail ? Pt : (it + 1 == pipe_main ? Ph : P);
                 launch_pko_spec(c, Pi, it, s);
                 if (it + 1 < g.max_iterations) hipLaunchKernelGGL(k_pick_correspond, dim3(P.nb), dim3(kBlock), 0, s, Pi, it);
                 else hipLaunchKernelGGL(k_pick, dim3(1), dim3(kBlock), 0, s, Pi, it);
             }
-            hipLaunchKernelGGL(k_wait_final, dim3(1), dim3(kWave), 0, c->stream, c->d_fin, seq, c->d_st, c->d_hbroken,
-                               c->pipe_bound);
+            if (defer) {                                  // enqueued by the next pipelined scan, or by flush_hold
+                c->hold_seq = seq;
+                c->hold_st = c->d_st;
+            } else {
+                hipLaunchKernelGGL(k_wait_final, dim3(1), dim3(kWave), 0, c->stream, c->d_fin, seq, c->d_st, c->d_hbroken,
+                                   c->pipe_bound);
+            }
             LO_HIP(c, hipGetLastError());
             if (timed) LO_HIP(c, hipEventRecord(c->ev1, c->stream));
             c->pending = true;
             return LO_OK;
         }
+        const int rcf = flush_hold(c);                    // (none pending unless the pipeline was just switched off)
+        if (rcf != LO_OK) return rcf;
         for (int it = 0; it < g.max_iterations; ++it) {
             if (!fused) {
                 if (it == 0) launch_correspond_first(c, P0, c->kd);
@@ -372,6 +489,7 @@ int lo_icp_optimize_async(lo_ctx* c, const float* d_pts, size_t n, const float T
 int lo_icp_result(lo_ctx* c, float T_out[12], lo_iter_log* logs, lo_stats* st) {
     if (!c) return LO_ERR_ARG;
     if (!c->pending) { c->err = "no optimize in flight"; return LO_ERR_STATE; }
+    { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
     // state header + the executed iterations' logs only
     const size_t bytes = offsetof(DevState, logs) + sizeof(lo_iter_log) * static_cast<size_t>(c->cfg.max_iterations);
     LO_HIP(c, hipMemcpyAsync(c->h_st, c->d_st, bytes, hipMemcpyDeviceToHost, c->stream));
@@ -393,6 +511,7 @@ int lo_icp_result(lo_ctx* c, float T_out[12], lo_iter_log* logs, lo_stats* st) {
         const bool timed = c->sync_call;
         rc = enqueue_optimize(c, c->last_pts, c->last_n, T0, c->last_ndev);
         c->sync_call = timed;
+        if (rc == LO_OK) rc = flush_hold(c);
         if (rc != LO_OK) return rc;
         LO_HIP(c, hipMemcpyAsync(c->h_st, c->d_st, bytes, hipMemcpyDeviceToHost, c->stream));
         LO_HIP(c, hipStreamSynchronize(c->stream));
@@ -410,6 +529,7 @@ int lo_icp_result(lo_ctx* c, float T_out[12], lo_iter_log* logs, lo_stats* st) {
         const bool timed = c->sync_call;
         rc = enqueue_optimize(c, c->last_pts, c->last_n, T0, c->last_ndev);
         c->sync_call = timed;
+        if (rc == LO_OK) rc = flush_hold(c);
         if (rc != LO_OK) return rc;
         LO_HIP(c, hipMemcpyAsync(c->h_st, c->d_st, bytes, hipMemcpyDeviceToHost, c->stream));
         LO_HIP(c, hipStreamSynchronize(c->stream));
@@ -443,11 +563,17 @@ int lo_sync(lo_ctx* c) {
     return LO_OK;
 }
 
+int lo_icp_flush(lo_ctx* c) {
+    if (!c) return LO_ERR_ARG;
+    return flush_hold(c);
+}
+
 int lo_icp_optimize(lo_ctx* c, const float* pts, size_t n, const float T_init[12], float T_out[12],
                     lo_iter_log* logs, lo_stats* st) {
     if (!c || !T_init || !T_out || (n > 0 && !pts)) return LO_ERR_ARG;
     if (n > static_cast<size_t>(c->cfg.max_points)) { c->err = "n exceeds max_points"; return LO_ERR_CAPACITY; }
     LO_HIP(c, hipSetDevice(c->device));
+    { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
     if (n > 0) LO_HIP(c, hipMemcpyAsync(c->d_pts, pts, n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     c->last_dev_count = false;
     c->nf_valid = false;
@@ -586,7 +712,8 @@ int lo_icp_optimize_loop(lo_ctx* c, const float* curr, size_t n_curr, const floa
         return LO_ERR_ARG;
     if (n_curr > static_cast<size_t>(c->cfg.max_points)) { c->err = "n_curr exceeds max_points"; return LO_ERR_CAPACITY; }
     LO_HIP(c, hipSetDevice(c->device));
-    int rc = kd_alloc(c);
+    int rc = flush_hold(c);
+    if (rc == LO_OK) rc = kd_alloc(c);
     if (rc != LO_OK) return rc;
     // local map of the matched keyframe: its feature cloud in the world (transform_point_cloud, :60-64)
     const lo::SE3f Tm = lo::se3_from12(T_matched);
@@ -612,7 +739,8 @@ int lo_icp_optimize_loop_dev(lo_ctx* c, const float* d_curr, size_t n_curr, cons
         return LO_ERR_ARG;
     if (n_curr > static_cast<size_t>(c->cfg.max_points)) { c->err = "n_curr exceeds max_points"; return LO_ERR_CAPACITY; }
     LO_HIP(c, hipSetDevice(c->device));
-    int rc = kd_alloc(c);
+    int rc = flush_hold(c);
+    if (rc == LO_OK) rc = kd_alloc(c);
     if (rc != LO_OK) return rc;
     rc = loop_map_from_device(c, c->lgrid, d_matched, n_matched, T_matched, kLoopMinPerCell);
     if (rc != LO_OK) return rc;
@@ -639,6 +767,7 @@ int lo_icp_optimize_raw_async(lo_ctx* c, const float* d_raw, size_t n_raw, int s
     int rc = check_raw_args(c, n_raw, stride, voxel_size);
     if (rc != LO_OK) return rc;
     LO_HIP(c, hipSetDevice(c->device));
+    { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
     int m = 0;
     LO_HIP(c, vf_enqueue(c->vf, d_raw, n_raw, stride, voxel_size, c->d_pts, c->stream, m));
     c->last_dev_count = true;
@@ -662,6 +791,7 @@ int lo_icp_optimize_raw(lo_ctx* c, const float* raw, size_t n_raw, int stride, f
     int rc = check_raw_args(c, n_raw, stride, voxel_size);
     if (rc != LO_OK) return rc;
     LO_HIP(c, hipSetDevice(c->device));
+    { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
     const float* src = n_raw > 0 ? pinned_alias(raw) : nullptr;
     if (!src) {                                          // pageable: stage the scan in device memory
         rc = stage_raw(c, raw, n_raw);
@@ -680,6 +810,7 @@ long long lo_filtered_points(lo_ctx* c, float* out, size_t cap) {
     if (!c->last_dev_count || !c->vf.n_out) { c->err = "no device-filtered scan"; return LO_ERR_STATE; }
     if (!out && c->nf_valid && !c->pending) return *c->h_nf;   // read back with the scan's result (lo_icp_result)
     LO_HIP(c, hipSetDevice(c->device));
+    { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
     int n = 0;
     LO_HIP(c, hipMemcpyAsync(&n, c->vf.n_out, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     LO_HIP(c, hipStreamSynchronize(c->stream));
@@ -696,7 +827,8 @@ long long lo_voxel_filter_gpu(lo_ctx* c, const float* raw, size_t n_raw, float v
     int rc = check_raw_args(c, n_raw, stride, voxel_size);
     if (rc != LO_OK) return rc;
     LO_HIP(c, hipSetDevice(c->device));
-    rc = stage_raw(c, raw, n_raw);
+    rc = flush_hold(c);
+    if (rc == LO_OK) rc = stage_raw(c, raw, n_raw);
     if (rc != LO_OK) return rc;
     int m = 0;
     LO_HIP(c, vf_enqueue(c->vf, c->d_raw, n_raw, stride, voxel_size, c->d_pts, c->stream, m));

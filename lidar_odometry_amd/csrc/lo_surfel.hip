@@ -13,6 +13,7 @@ extern "C" {
 
 int lo_map_set_surfels(lo_ctx* c, const int32_t* keys, const float* normals, const float* centroids, size_t m) {
     if (!c) return LO_ERR_ARG;
+    { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
     if (m > 0 && (!keys || !normals || !centroids)) { c->err = "null surfel arrays"; return LO_ERR_ARG; }
     size_t cap = 2;
     uint32_t l2 = 1;
@@ -67,6 +68,7 @@ void ctx_set_map_source(lo_ctx* c, uint64_t src, uint64_t epoch, uint64_t pos) {
 
 int ctx_reserve_table(lo_ctx* c, size_t min_slots, void** tab, uint32_t* log2cap, uint64_t* gen) {
     if (!c || !tab || !log2cap || !gen) return LO_ERR_ARG;
+    { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
     size_t cap = 2;
     uint32_t l2 = 1;
     while (cap < min_slots) { cap <<= 1; ++l2; }
@@ -98,6 +100,7 @@ int ctx_reserve_table(lo_ctx* c, size_t min_slots, void** tab, uint32_t* log2cap
 
 int ctx_filtered_device(lo_ctx* c, const float** d_pts, const int** d_n) {
     if (!c || !d_pts || !d_n) return LO_ERR_ARG;
+    { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
     if (!c->last_dev_count || !c->vf.n_out) { c->err = "no device-filtered scan"; return LO_ERR_STATE; }
     *d_pts = c->d_pts;
     *d_n = c->vf.n_out;
@@ -141,6 +144,7 @@ static int reconcile_fit(lo_ctx* c) {
 int ctx_fit_surfels(lo_ctx* c, const int32_t* keys, const int32_t* offs, size_t n_jobs, const float* cs, size_t n_cs,
                     float thr, uint64_t* ticket) {
     if (!c || !ticket || (n_jobs > 0 && (!keys || !offs || !cs))) return LO_ERR_ARG;
+    { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
     if (!c->d_tab) { c->err = "no surfel table to patch"; return LO_ERR_STATE; }
     int rc0 = reconcile_fit(c);                          // a superseded ticket's failures must not stay resident
     if (rc0 != LO_OK) return rc0;
@@ -224,6 +228,7 @@ extern "C" {
 int lo_map_patch_surfels(lo_ctx* c, const int32_t* keys, const float* normals, const float* centroids,
                          const uint8_t* present, size_t m) {
     if (!c) return LO_ERR_ARG;
+    { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
     if (m == 0) return LO_OK;
     if (!keys || !normals || !centroids || !present) { c->err = "null patch arrays"; return LO_ERR_ARG; }
     if (!c->d_tab) { c->err = "no surfel table to patch"; return LO_ERR_STATE; }
@@ -292,6 +297,7 @@ int lo_map_patch_surfels(lo_ctx* c, const int32_t* keys, const float* normals, c
 int lo_map_sync_surfels(lo_ctx* c, const int32_t* keys, const float* normals, const float* centroids, size_t m,
                         int* patched) {
     if (!c) return LO_ERR_ARG;
+    { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
     if (m > 0 && (!keys || !normals || !centroids)) { c->err = "null surfel arrays"; return LO_ERR_ARG; }
     if (c->kd) { c->err = "KDTree-mode context (lo_map_set_points)"; return LO_ERR_STATE; }
     std::unordered_map<uint64_t, size_t> in;
