@@ -190,11 +190,11 @@ int lo_set_pipeline(lo_ctx* ctx, int enable, int main_iterations);
  * WHO GAINS: only a caller that enqueues scan k + 1 with NO library call on the context since scan k.  Every other
  * call -- lo_icp_result, lo_icp_export_pose, lo_stream, a map call, a setter -- enqueues the pending hold first, so a
  * caller that reads or exports each scan's result before the next enqueue gets no overlap and runs exactly as with
- * overlap off (same launches, same split).  A scan's record cannot be taken later either: only the last queued scan's
- * state is readable.  So this is throughput for a stream of scans with initial poses known up front of which only the
- * last result (or none: warm-up, a rate measurement) is read per queue; a caller that needs every pose -- relocalisation
- * candidates, re-registration, scan-parallel ranks that gather each pose -- gains nothing today, and neither does a
- * frame loop whose T_init comes from the previous pose.  The time from a scan's first launch to its result does not
+ * overlap off (same launches, same split).  So this is throughput for a stream of scans with initial poses known up
+ * front whose results are read once per queue: the last one with lo_icp_result, or all of them (up to 64) with
+ * lo_icp_queue_records, below -- relocalisation candidates, re-registration, N poses against one map.  A frame loop
+ * whose T_init comes from the previous pose gains nothing, and neither do scan-parallel ranks that export each pose
+ * on the stream (lo_icp_export_pose flushes).  The time from a scan's first launch to its result does not
  * change.  Results are identical with overlap on or off.
  * CHANGED CONTRACT (default on): two rules that did not exist before this switch --
  *  - work a caller enqueues on a shared stream ITSELF after lo_icp_optimize_async is ordered after the scan's final
@@ -205,12 +205,36 @@ int lo_set_pipeline(lo_ctx* ctx, int enable, int main_iterations);
  *    call lo_icp_flush first, or switch the overlap off.
  * NOTE lo_stream: it is a getter that may launch the pending hold (whoever asks for the stream is about to enqueue on
  * it; the device map, the loop detector and the map builder take it this way); poll the handle once, not in a loop.
- * lo_scan_overlap_status: out[0] enabled, out[1] scans whose head was enqueued in front of the previous scan's hold. */
+ * lo_scan_overlap_status: out[0] enabled, out[1] scans whose head was enqueued in front of the previous scan's hold.
+ * TWO SCANS IN FLIGHT (lo_set_scan_depth, default 2; LO_OVERLAP_DEPTH=1 in the environment, or depth 1 here, gives the
+ * one pending hold described above, launch for launch).  With depth 2 a queued scan k enqueues the hold of scan k - 2
+ * -- the scan that last used its set of per-scan state -- in front of its own head, and no longer the hold of scan
+ * k - 1: up to two holds are pending, each scan's tail has its own stream, and scan k's Gauss-Newton iterations run
+ * beside scan k - 1's tail.  The scans of a queue may therefore become final out of order; each is final before the
+ * scan two places later starts.  Who gains, what flushes and the two rules above are unchanged: lo_icp_flush and every
+ * other library call enqueue ALL pending holds, oldest first, and the buffers of the LAST TWO queued scans are still
+ * the ones that must stay valid and unchanged (the hold of scan k - 2 sits on the context stream in front of scan k,
+ * and what is left of that scan's tail leaves before touching its points).  Results are identical for either depth.
+ * Unless a depth was chosen here or in the environment, a context keeps ONE scan in flight while other contexts of the
+ * process have queued scans in flight: their launches already fill the chip, and more streams only crowd the hardware
+ * queues they share.  lo_set_scan_depth: LO_ERR_ARG for a depth other than 1 or 2. */
 int lo_set_scan_overlap(lo_ctx* ctx, int enable);
 int lo_scan_overlap_status(lo_ctx* ctx, long long out[2]);
-/* Enqueue the pending hold of the last queued scan on the context stream now (no-op when there is none): what follows
- * on that stream sees the scan's final result.  Does not wait on the host. */
+int lo_set_scan_depth(lo_ctx* ctx, int depth);
+/* Enqueue the pending holds of the last queued scans (at most two) on the context stream now, oldest first (no-op when
+ * there is none): what follows on that stream sees those scans' final results.  Does not wait on the host. */
 int lo_icp_flush(lo_ctx* ctx);
+/* Every queued scan's record, not only the last one's.  Each pipelined scan (a small surfel scan with PKO while the
+ * scan pipeline is on: the scans that can overlap, and the same scans made through a synchronous call) leaves a
+ * 16-float record -- lo_icp_export_pose's layout: pose[12], status, iterations, n_corr, 0 -- in a device ring of 64
+ * records per context, written by the device thread that makes the scan final.  lo_icp_queue_records enqueues the
+ * pending holds, drains the context's streams and copies the records of the last n_last such scans to out16xN
+ * (host memory, 16 * n_last floats), oldest first; the queue stays as fast as one whose results nobody reads.
+ * LO_ERR_ARG: n_last > 64, or more than were queued since the last optimize that was NOT pipelined (a large or an empty
+ * scan, a KDTree-mode scan, any scan while the pipeline is off) or since a pipeline timeout.  LO_ERR_PIPELINE:
+ * a device-side wait timed out while the queue ran (lo_pipeline_status); the pipeline is then off and the records of
+ * that queue are not returned.  lo_icp_result still returns the last scan's result afterwards. */
+int lo_icp_queue_records(lo_ctx* ctx, int n_last, float* out16xN);
 /* IterativeClosestPointOptimizer::update_config (IterativeClosestPointOptimizer.h:220): new parameters, same context --
  * the device map, buffers and stream stay.  voxel_size, hierarchy_factor, max_points and use_surfel_correspondence
  * are fixed at lo_create (LO_ERR_STATE); new PKO parameters rebuild the PKO tables. */

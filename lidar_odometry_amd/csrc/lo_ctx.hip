@@ -7,11 +7,13 @@
 #include "lo_ctx_def.h"
 
 namespace lo {
-// Both streams of the context drained (lo_sync, lo_set_stream, lo_destroy).
+// All streams of the context drained (lo_sync, lo_set_stream, lo_destroy): the pending holds first, then the context
+// stream and both lanes' tail streams.
 hipError_t sync_all(lo_ctx* c) {
     if (c->stream && flush_hold(c) != LO_OK) return hipErrorUnknown;   // (the text is in c->err)
     hipError_t e = c->stream ? hipStreamSynchronize(c->stream) : hipSuccess;
-    if (e == hipSuccess && c->s_tail) e = hipStreamSynchronize(c->s_tail);
+    for (hipStream_t s : c->s_tail)
+        if (e == hipSuccess && s) e = hipStreamSynchronize(s);
     return e;
 }
 }  // namespace lo
@@ -216,6 +218,7 @@ lo_ctx* lo_create(const lo_config* cfg, int device, int* err) {
     if (const char* pp = std::getenv("LO_PIPE")) c->pipe = std::atoi(pp) != 0;
     if (const char* pm = std::getenv("LO_PIPE_MAIN")) { c->pipe_main = std::max(1, std::atoi(pm)); c->pipe_main_auto = false; }
     if (const char* po = std::getenv("LO_OVERLAP")) c->overlap = std::atoi(po) != 0;
+    if (const char* pd = std::getenv("LO_OVERLAP_DEPTH")) { c->depth = std::atoi(pd) <= 1 ? 1 : 2; c->depth_auto = false; }
     if (const char* pw = std::getenv("LO_PIPE_WAIT_MS")) c->pipe_bound = 100000ull * std::max(1, std::atoi(pw));
     if (const char* pf = std::getenv("LO_PIPE_FAIL_AT")) c->pipe_fail_at = static_cast<uint32_t>(std::max(0, std::atoi(pf)));
     if (const char* pg = std::getenv("LO_PKO_GROUPS")) c->pko_groups = std::max(0, std::atoi(pg));
@@ -244,7 +247,8 @@ void lo_destroy(lo_ctx* c) {
     }
     (void)hipSetDevice(c->device);
     (void)sync_all(c);
-    if (c->s_tail) (void)hipStreamDestroy(c->s_tail);
+    for (hipStream_t s : c->s_tail)
+        if (s) (void)hipStreamDestroy(s);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (hipEvent_t e : c->st_ev) (void)hipEventDestroy(e);
@@ -331,6 +335,15 @@ int lo_set_scan_overlap(lo_ctx* c, int enable) {
     const int rc = flush_hold(c);
     if (rc != LO_OK) return rc;
     c->overlap = enable != 0;
+    return LO_OK;
+}
+
+int lo_set_scan_depth(lo_ctx* c, int depth) {
+    if (!c || depth < 1 || depth > 2) return LO_ERR_ARG;
+    const int rc = flush_hold(c);
+    if (rc != LO_OK) return rc;
+    c->depth = depth;
+    c->depth_auto = false;
     return LO_OK;
 }
 

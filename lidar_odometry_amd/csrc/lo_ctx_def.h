@@ -176,10 +176,13 @@ struct lo_ctx {
     int pko_groups = 0;             // EM workgroups per PKO launch (lo_set_pko_groups / LO_PKO_GROUPS; 0 = one per alpha)
     bool pko_solo = false;          // LO_PKO_SOLO=1 (A/B): the speculative PKO launch asks for enough LDS that one
                                     //   workgroup holds a CU alone (no other launch's waves on its SIMDs)
-    hipStream_t s_tail = nullptr;
-    uint32_t pipe_seq = 0;
-    DevBuf<uint32_t> d_fin;         // [0] the last scan whose result is final (publish_final), [1] main part done,
-                                    // [2] signal_main's block count, [3] broken (a wait timed out; sticky)
+    hipStream_t s_tail[2] = {nullptr, nullptr};   // one tail stream per lane (scan overlap, below): a scan's tail does not
+                                    //   queue behind the early-exit launches of the other lane's scan
+    uint32_t pipe_seq = 0;          // pipelined scans so far (LO_PIPE_FAIL_AT counts in it)
+    uint32_t lane_seq[2] = {0, 0};  // each lane's own sequence number: what its fence words count in (never 0)
+    DevBuf<uint32_t> d_fin;         // kFinWords per lane (KParams::fin names the lane's group): [0] the lane's last scan
+                                    // whose result is final (publish_final), [1] main part done, [2] signal_main's block
+                                    // count, [3] broken (a wait timed out; sticky, and set in both groups: pipe_fail)
     MappedBuf<uint32_t> h_broken;   // device-mapped: the seq of the scan whose wait timed out (0: none)
     uint32_t* d_hbroken = nullptr;  //   its device alias (not owned)
     unsigned long long pipe_bound = 200000000ull;   // wait bound in 100 MHz ticks (2 s; LO_PIPE_WAIT_MS)
@@ -193,7 +196,7 @@ struct lo_ctx {
     // above are the lane of the last enqueued scan, `alt` is the other one (allocated the first time a scan is enqueued
     // while another is in flight), and lane_switch swaps them.  Every other entry point that touches the context stream
     // or a queued scan's inputs enqueues the pending hold first (flush_hold), after which the context is as it was
-    // before this existed.  The map, the PKO tables and the d_fin words are shared.
+    // before this existed.  The map and the PKO tables are shared; each lane has its own fence words and tail stream.
     struct ScanLane {
         DevBuf<int32_t> d_slot;
         DevBuf<double> d_res_pko;
@@ -209,8 +212,23 @@ struct lo_ctx {
     bool alt_ready = false;         // alt holds a full set, its candidate buffers sized for the current alpha grid
     int lane = 0;                   // which set the members above are (scan k of an overlapped run: k & 1)
     bool overlap = true;
-    uint32_t hold_seq = 0;          // the scan whose k_wait_final is still to be enqueued (0: none)
-    DevState* hold_st = nullptr;    //   and its lane's DevState (a timed-out wait marks it LO_ERR_PIPELINE)
+    // Two scans in flight (lo_set_scan_depth; depth 2 by default, LO_OVERLAP_DEPTH=1 for one): the hold of scan k - 1 is
+    // no longer enqueued by scan k, only the hold of scan k - 2 -- the scan that last used scan k's lane -- and in front
+    // of scan k's head.  So up to `depth` holds are pending, and scan k's GN iterations run beside scan k - 1's tail.
+    struct Hold {
+        uint32_t seq;               // the scan's number on its lane
+        int lane;
+        DevState* st;               // its lane's DevState (a timed-out wait marks it LO_ERR_PIPELINE)
+    };
+    Hold holds[2];                  // the scans whose k_wait_final is still to be enqueued, oldest first
+    int n_hold = 0;
+    int depth = 2;
+    bool depth_auto = true;         // no depth chosen: one scan in flight while other contexts queue scans too (scan_depth)
+    int depth_used = 2;             // the depth the pending holds were placed for
+    // every pipelined scan's 16-float record (lo_icp_queue_records): the thread that publishes a scan final writes it
+    DevBuf<float> d_ring;           // kRingRecords x 16 floats
+    unsigned long long ring_pos = 0;   // pipelined scans given a slot so far (slot = ring_pos % kRingRecords)
+    unsigned ring_n = 0;            // of which the last ring_n were queued with no other scan in between (<= kRingRecords)
     unsigned long long overlapped = 0;   // scans whose head was enqueued in front of the previous scan's hold
     const float* last_pts = nullptr;   // the scan in flight (a re-run after a pipeline timeout)
     const int* last_ndev = nullptr;
@@ -220,6 +238,9 @@ struct lo_ctx {
 
 namespace lo {
 constexpr int kStageEvents = 1024;
+constexpr int kFinWords = 4;                          // fence words per lane (lo_ctx::d_fin; pipe_fail relies on the 4)
+constexpr int kRingRecords = 64;                      // lo_icp_queue_records: records kept per context
+constexpr int kRecWords = 16;                         //   floats per record (lo_icp_export_pose's layout)
 constexpr int kExactMaxPoints = 16384;                // reference-exact mode: one-workgroup sort in LDS up to here
 
 // lo_ctx.hip
@@ -242,7 +263,7 @@ void launch_pko_spec(lo_ctx* c, const KParams& P, int it, hipStream_t s = nullpt
 void launch_brute(lo_ctx* c, const KParams& P);
 void launch_correspond(lo_ctx* c, const KParams& P, int with_stats, bool kd);
 int enqueue_optimize(lo_ctx* c, const float* d_pts, size_t n, const float T_init[12], const int* n_dev = nullptr);
-int flush_hold(lo_ctx* c);     // the pending hold of the last pipelined scan, enqueued on the context stream now
+int flush_hold(lo_ctx* c);     // the pending holds of the last pipelined scans, enqueued on the context stream now
 
 // ---- per-scan helpers on the launch path of every optimize, single and batched: inline, as when one file held them
 // PKO workgroups: one alpha of the JS grid per workgroup (each fits the GMM redundantly), capped at kPkoMaxWGs

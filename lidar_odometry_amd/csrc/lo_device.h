@@ -164,9 +164,11 @@ struct KParams {
     const double* direct_res; // nullable: PKO on given residuals (parity entry point)
     unsigned long long* em_stat;  // nullable (stage timing on): DevState::em_stat, the lead PKO workgroup's EM timing
     DevState* st;
-    uint32_t* fin;            // nullable (scan pipeline, lo_set_pipeline): the context's "last final scan" word
+    uint32_t* fin;            // nullable (scan pipeline, lo_set_pipeline): the "last final scan" word of the scan's lane
                               //   (fin[1] main part done, fin[2] signal_main's block count, fin[3] pipeline broken)
-    uint32_t seq;             //   and this scan's sequence number, published there once its result is final
+    uint32_t seq;             //   and this scan's sequence number on that lane, published there once its result is final
+    float* rec;               // nullable: the scan's slot in the context's record ring (16 floats, k_export_pose's
+                              //   layout), written by the thread that publishes the scan final
     int hold;                 // 1: the main part's last pick (signal_main: fin[1] = seq once its correspondences are out;
                               //   fin[2] counts its blocks in)
     int tail;                 // 1: a tail-stream launch -- it leaves once scan seq is final (fin_reached; the DevState may
@@ -202,7 +204,8 @@ __device__ __forceinline__ bool wait_word2(const uint32_t* a, const uint32_t* b,
     return true;
 }
 
-// A tail-stream launch's own early-exit test (sc1 load: fresh across XCDs; the scans become final in order).
+// A tail-stream launch's own early-exit test (sc1 load: fresh across XCDs; a lane's scans become final in order -- the
+// next scan on the lane starts behind this one's k_wait_final -- while the other lane's may be final before or after).
 __device__ __forceinline__ bool fin_reached(const KParams& P) {
     return static_cast<int32_t>(__hip_atomic_load(P.fin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - P.seq) >= 0;
 }
@@ -212,8 +215,19 @@ __device__ __forceinline__ bool pipe_broken(const KParams& P) {
     return __hip_atomic_load(P.fin + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
 }
 __device__ __forceinline__ bool tail_gone(const KParams& P) { return P.tail && (fin_reached(P) || pipe_broken(P)); }
+// The calling thread has just written the scan's final DevState; the scan's record (lo_icp_queue_records) goes out with
+// it, ahead of the release, so whoever sees the fence word sees the record.
 __device__ __forceinline__ void publish_final(const KParams& P) {
     if (!P.fin) return;
+    if (P.rec) {
+        const DevState* st = P.st;
+#pragma unroll
+        for (int q = 0; q < 12; ++q) P.rec[q] = st->pose[q];
+        P.rec[12] = static_cast<float>(st->status);
+        P.rec[13] = static_cast<float>(st->iter);
+        P.rec[14] = static_cast<float>(st->n_corr);
+        P.rec[15] = 0.0f;
+    }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __hip_atomic_store(P.fin, P.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -464,12 +464,12 @@ __global__ void k_init(DevState* st, Pose12 T, double scale, double alpha) {
     }
 }
 
-// Scan pipeline (lo_set_pipeline), both bounded by wait_word:
-//   k_wait_seq   heads a scan's tail on the tail stream: the main part is done (fin[1] >= seq, signal_main) or the
-//                scan is already final (fin[0] >= seq: its tail launches only leave early);
+// Scan pipeline (lo_set_pipeline), both bounded by wait_word; fin is the group of fence words of the scan's lane:
+//   k_wait_seq   heads a scan's tail on its lane's tail stream: the main part is done (fin[1] >= seq, signal_main) or
+//                the scan is already final (fin[0] >= seq: its tail launches only leave early);
 //   k_wait_final follows the tail on the context stream: holds it until the scan's result is final (fin[0] >= seq).
 // Host submission order is main part, tail, k_wait_final: every wait depends only on work submitted before it, so
-// the two streams may share one hardware queue (they then simply run in order).  What breaks the device-side waits is a
+// the streams may share one hardware queue (they then simply run in order).  What breaks the device-side waits is a
 // dispatcher that serialises the two queues OUT of submission order (rocprofv3 counter collection runs one dispatch
 // at a time and can take the context stream's k_wait_final before the tail stream's launches: the wait then waits for
 // work that cannot start until it ends).  A wait that times out -- or finds the pipeline already broken -- marks the
@@ -478,7 +478,11 @@ __global__ void k_init(DevState* st, Pose12 T, double scale, double alpha) {
 // the pipeline off at its next enqueue and re-runs a synchronous call's scan on one stream).
 __device__ __forceinline__ void pipe_fail(uint32_t* fin, uint32_t* hbroken, uint32_t seq, DevState* st) {
     st->status = LO_ERR_PIPELINE;
-    __hip_atomic_store(fin + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // fin is one lane's group of four words; the two groups lie side by side in one 32-byte aligned block (lo_ctx::d_fin),
+    // and the broken word is set in both: a wait that timed out on either lane stops both
+    uint32_t* both = reinterpret_cast<uint32_t*>(reinterpret_cast<uintptr_t>(fin) & ~static_cast<uintptr_t>(31));
+    __hip_atomic_store(both + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(both + 7, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (hbroken) __hip_atomic_store(hbroken, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 __global__ void k_wait_seq(uint32_t* fin, uint32_t seq, DevState* st, uint32_t* hbroken, unsigned long long bound) {

@@ -5,6 +5,8 @@
 // between; the kernels read DevState::done and fall through once the scan has converged or failed.
 #include <hipcub/hipcub.hpp>
 
+#include <atomic>
+
 #include "lo_ctx_def.h"
 
 namespace lo {
@@ -52,12 +54,15 @@ static void launch_gn_tail(lo_ctx* c, const KParams& P, int it) {
     }
 }
 
-// Scan pipeline (first pipelined scan): the tail stream and the two flag words.
+// Scan pipeline (first pipelined scan): the lanes' tail streams, their fence words, the record ring, the host flag.
 static int pipe_alloc(lo_ctx* c) {
     if (c->d_hbroken) return LO_OK;                 // set last
-    if (!c->s_tail) LO_HIP(c, hipStreamCreateWithFlags(&c->s_tail, hipStreamNonBlocking));
-    LO_HIP(c, c->d_fin.reserve(4));
-    LO_HIP(c, hipMemset(c->d_fin, 0, 4 * sizeof(uint32_t)));
+    // (the first lane's tail stream; the second lane's is made when a scan first runs there with two in flight)
+    if (!c->s_tail[0]) LO_HIP(c, hipStreamCreateWithFlags(&c->s_tail[0], hipStreamNonBlocking));
+    LO_HIP(c, c->d_fin.reserve(2 * kFinWords));     // (pipe_fail finds both groups from either: 32 bytes, aligned)
+    LO_HIP(c, hipMemset(c->d_fin, 0, 2 * kFinWords * sizeof(uint32_t)));
+    LO_HIP(c, c->d_ring.reserve(static_cast<size_t>(kRingRecords) * kRecWords));
+    LO_HIP(c, hipMemset(c->d_ring, 0, static_cast<size_t>(kRingRecords) * kRecWords * sizeof(float)));
     LO_HIP(c, c->h_broken.reserve(1));
     *c->h_broken = 0;
     LO_HIP(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_hbroken), c->h_broken, 0));
@@ -65,38 +70,60 @@ static int pipe_alloc(lo_ctx* c) {
     return LO_OK;
 }
 
-// A pipeline wait timed out (the dispatcher ran the two streams out of submission order): drain both streams, switch
+// A pipeline wait timed out (the dispatcher ran the streams out of submission order): drain all three streams, switch
 // the pipeline off for this context, clear the flag words.  Scans enqueued before this point report LO_ERR_PIPELINE
 // (their tails left without touching anything); a synchronous call re-runs its scan on one stream (lo_icp_result).
 static int pipe_recover(lo_ctx* c) {
-    LO_HIP(c, sync_all(c));                         // (enqueues a pending hold of either lane first: it gives up at once)
+    LO_HIP(c, sync_all(c));                         // (enqueues the pending holds of both lanes first: they give up at once)
     c->pipe = false;
     ++c->pipe_timeouts;
-    c->err = "scan pipeline: a device-side wait timed out (the two streams were not run concurrently, e.g. rocprofv3 "
+    c->ring_n = 0;                                  // (the records of the scans that gave up were never written)
+    c->err = "scan pipeline: a device-side wait timed out (the streams were not run concurrently, e.g. rocprofv3 "
              "counter collection); pipeline switched off for this context";
-    LO_HIP(c, hipMemset(c->d_fin, 0, 4 * sizeof(uint32_t)));
+    LO_HIP(c, hipMemset(c->d_fin, 0, 2 * kFinWords * sizeof(uint32_t)));
+    c->lane_seq[0] = c->lane_seq[1] = 0;            // (with the words they count in)
     LO_HIP(c, hipStreamSynchronize(nullptr));
     __atomic_store_n(c->h_broken.get(), 0u, __ATOMIC_RELEASE);
     return LO_OK;
 }
 static bool pipe_flagged(const lo_ctx* c) { return c->h_broken && __atomic_load_n(c->h_broken.get(), __ATOMIC_ACQUIRE) != 0u; }
 
-// Scan overlap: the one place a pending hold leaves the host.  Called at the top of every entry point that enqueues on
-// the context stream, reads from it, or changes what a queued scan reads (and by sync_all); enqueue_optimize calls it
-// after the next scan's head instead.  The wait is k_wait_final's as before: bounded by pipe_bound, it gives up at once
-// when the pipeline is broken, and a timeout marks the held scan's own DevState (its lane's) LO_ERR_PIPELINE.
-int flush_hold(lo_ctx* c) {
-    if (c->hold_seq == 0) return LO_OK;
-    const uint32_t seq = c->hold_seq;
-    DevState* st = c->hold_st;
-    c->hold_seq = 0;
-    c->hold_st = nullptr;
+// Contexts of this process with a hold pending, i.e. with queued scans in flight right now.
+static std::atomic<int> g_holding{0};
+// Scan overlap: the one place a pending hold leaves the host -- the oldest one, on the context stream.  The wait is
+// k_wait_final's as before: bounded by pipe_bound, it gives up at once when the pipeline is broken, and a timeout marks
+// the held scan's own DevState (its lane's) LO_ERR_PIPELINE.
+static int pop_hold(lo_ctx* c) {
+    const lo_ctx::Hold h = c->holds[0];
+    c->holds[0] = c->holds[1];
+    if (--c->n_hold == 0) g_holding.fetch_sub(1, std::memory_order_relaxed);
     LO_HIP(c, hipSetDevice(c->device));
-    hipLaunchKernelGGL(k_wait_final, dim3(1), dim3(kWave), 0, c->stream, c->d_fin, seq, st, c->d_hbroken, c->pipe_bound);
+    hipLaunchKernelGGL(k_wait_final, dim3(1), dim3(kWave), 0, c->stream, c->d_fin + kFinWords * h.lane, h.seq, h.st,
+                       c->d_hbroken, c->pipe_bound);
     LO_HIP(c, hipGetLastError());
     return LO_OK;
 }
+// All pending holds, oldest first.  Called at the top of every entry point that enqueues on the context stream, reads
+// from it, or changes what a queued scan reads (and by sync_all); enqueue_optimize places the holds of a queue of scans
+// itself (pop_hold).
+int flush_hold(lo_ctx* c) {
+    while (c->n_hold > 0) {
+        const int rc = pop_hold(c);
+        if (rc != LO_OK) return rc;
+    }
+    return LO_OK;
+}
 
+// Scans in flight for the scan being enqueued.  Two pay while the chip is half idle under one context's queue; when
+// other contexts of the process are queueing scans too, their launches already fill it, and a second scan in flight per
+// context only adds waits to the few hardware queues all their streams share (8 contexts: 24 streams on 4 queues ran
+// 31 % slower in aggregate).  So unless lo_set_scan_depth / LO_OVERLAP_DEPTH chose, a context that is not alone in
+// having scans in flight keeps one.
+static int scan_depth(const lo_ctx* c) {
+    if (!c->depth_auto) return c->depth;
+    const int others = g_holding.load(std::memory_order_relaxed) - (c->n_hold > 0 ? 1 : 0);
+    return others > 0 ? 1 : c->depth;
+}
 // A small scan whose PKO launches pre-solve the candidates (k_pick* selects one): the launch sequence of the fast mode,
 // in reference-exact mode with the one-workgroup sort.  enqueue_optimize computes this once, before the lanes are
 // chosen, and every branch below tests it; the KParams it is later built into must agree (checked there).
@@ -113,7 +140,8 @@ static bool pipelined_scan(const lo_ctx* c, bool cand, int pipe_main) {
 }
 
 // The second lane: a full set of the per-scan state (same sizes as ctx_alloc's and ensure_acc_part's), then the swap.
-// Nothing of the lane swapped in is in flight: its last scan's hold was enqueued before the scan now pending started.
+// Depth 1: nothing of the lane swapped in is in flight, its last scan's hold was enqueued before the scan now pending
+// started.  Depth 2: that hold may still be pending, and the caller enqueues it before anything touches the lane.
 static int lane_switch(lo_ctx* c) {
     lo_ctx::ScanLane& A = c->alt;
     if (!c->alt_ready) {
@@ -320,6 +348,8 @@ int enqueue_optimize(lo_ctx* c, const float* d_pts, size_t n, const float T_init
     c->last_n = n;
     c->last_pts = d_pts;
     c->last_ndev = n_dev;
+    const unsigned ring_n0 = c->ring_n;                   // the run of pipelined scans ends here unless this is one
+    c->ring_n = 0;
     // reset the GN state (pose by kernel argument: no host staging buffer, scans can queue back to back)
     Pose12 T0;
     std::memcpy(T0.v, T_init, sizeof(float) * 12);
@@ -331,21 +361,33 @@ int enqueue_optimize(lo_ctx* c, const float* d_pts, size_t n, const float T_init
     // whose points are the caller's: a device-filtered scan sits in the context's one point buffer, which the next
     // raw call's filter overwrites, so that call enqueues the hold first anyway
     const bool cand = cand_scan(c, n);
+    const int depth = scan_depth(c);
+    if (depth != c->depth_used) {                         // the holds pending were placed for the other order: all out first
+        const int rcd = flush_hold(c);
+        if (rcd != LO_OK) return rcd;
+        c->depth_used = depth;
+    }
     const bool may_defer = c->overlap && !timed && !c->stage_timing && !n_dev && !pipe_flagged(c);
     // this scan's head overlaps: a hold is pending and the scan is pipelined.  Only then does it take the queue's split
     // (pipe_main, 1 by default): the caller is queueing scans back to back, and the next head hides under a longer tail.
     // A scan behind a flushed hold (its caller read the previous result, or made any other call) keeps the split 2 a
     // scan always had unless one was chosen -- split 1 without overlap costs about 1 %.
-    const bool overlaps = c->hold_seq != 0 && may_defer && pipelined_scan(c, cand, c->pipe_main);
+    const bool overlaps = c->n_hold != 0 && may_defer && pipelined_scan(c, cand, c->pipe_main);
     const int pipe_main = (c->pipe_main_auto && !overlaps) ? 2 : c->pipe_main;
     const bool defer = may_defer && pipelined_scan(c, cand, pipe_main);
-    if (c->hold_seq != 0) {
+    if (c->n_hold != 0) {
         if (!overlaps) {                                  // any other path: the context as it always was
             const int rcf = flush_hold(c);
             if (rcf != LO_OK) return rcf;
         } else {                                          // this scan's state goes to the other lane
             const int rcl = lane_switch(c);
             if (rcl != LO_OK) return rcl;
+            // ... which the scan before the previous one used.  Two scans in flight: its hold is still pending, and
+            // goes in front of this scan's head, which rewrites the state that scan's tail reads.
+            if (depth > 1 && c->holds[0].lane == c->lane) {
+                const int rch = pop_hold(c);
+                if (rch != LO_OK) return rch;
+            }
         }
     }
     if (timed) LO_HIP(c, hipEventRecord(c->ev0, c->stream));
@@ -396,45 +438,67 @@ int enqueue_optimize(lo_ctx* c, const float* d_pts, size_t n, const float T_init
             // is final
             const int rc2 = pipe_alloc(c);
             if (rc2 != LO_OK) return rc2;
-            if (++c->pipe_seq == 0) c->pipe_seq = 1;      // 0 is the fence word's reset value, never a scan's number
-            const uint32_t seq = c->pipe_seq;
-            P.fin = P0.fin = c->d_fin;
+            if (++c->pipe_seq == 0) c->pipe_seq = 1;      // (the test hook's count: LO_PIPE_FAIL_AT is never 0)
+            const bool fail = c->pipe_fail_at != 0 && c->pipe_seq == c->pipe_fail_at;
+            const int lane = c->lane;
+            if (++c->lane_seq[lane] == 0) c->lane_seq[lane] = 1;   // 0 is the fence word's reset value, never a scan's number
+            const uint32_t seq = c->lane_seq[lane];
+            uint32_t* const fin = c->d_fin + kFinWords * lane;
+            // one scan in flight: both lanes' tails on the first tail stream, as before there were two -- tail(k) starts
+            // behind tail(k - 1) anyway, and a third stream per context only crowds the hardware queues of a process
+            // that runs many contexts
+            const int tl = depth > 1 ? lane : 0;
+            if (!c->s_tail[tl]) LO_HIP(c, hipStreamCreateWithFlags(&c->s_tail[tl], hipStreamNonBlocking));
+            const hipStream_t s_tail = c->s_tail[tl];
+            P.fin = P0.fin = fin;
             P.seq = P0.seq = seq;
+            P.rec = P0.rec = c->d_ring + static_cast<size_t>(c->ring_pos % kRingRecords) * kRecWords;
+            ++c->ring_pos;
+            c->ring_n = std::min<unsigned>(ring_n0 + 1, kRingRecords);
             KParams Pt = P;                               // tail launches: leave once scan seq is final (the
             Pt.tail = 1;                                  // DevState may already be the next scan's)
             KParams Ph = P;                               // the main part's last pick signals the tail (signal_main)
             Ph.hold = 1;
-            // host submission order, scan k: head(k) -> k_wait_final(k - 1) -> main(k) on the context stream, then
-            // k_wait_seq(k) -> tail(k) on the tail stream; k_wait_final(k) follows head(k + 1), or comes from flush_hold.
-            // Every device-side wait depends only on work submitted before it, on any stream: k_wait_final(k - 1) polls
-            // the word that main(k - 1) or tail(k - 1) publishes, both submitted during the previous call, and
-            // k_wait_seq(k) polls the word main(k)'s last pick sets, submitted just above it.  So the order is
-            // deadlock-free even if both streams share one hardware queue (they then simply run in this order).
-            // head(k) runs on the lane that scan k - 2 used: k_wait_final(k - 2) precedes main(k - 1) on this stream, so
-            // that scan is final, and what is left of its tail leaves on tail_gone before touching anything.
+            // host submission order of a queue of scans, scan k on lane k & 1 (two in flight, the default):
+            //   context stream:   k_wait_final(k - 2) -> head(k) -> main(k)        (the wait was placed above)
+            //   tail stream k & 1: k_wait_seq(k) -> tail(k)
+            // and k_wait_final(k) is placed by scan k + 2, or by flush_hold.  With one scan in flight (depth 1) the
+            // context stream carries head(k) -> k_wait_final(k - 1) -> main(k) instead.
+            // Every device-side wait depends only on work submitted before it, on any stream: k_wait_final(j) polls
+            // the lane's word that main(j) or tail(j) publishes, both submitted during scan j's own call, which
+            // returned before any call that can place that wait; k_wait_seq(k) polls the lane's word that main(k)'s
+            // last pick sets, submitted just above it, or the one main(k) publishes when it ends the scan.  Nothing
+            // waits for a later submission, so the order is deadlock-free even if all three streams share one hardware
+            // queue (they then simply run in this order), and every wait is bounded by pipe_bound besides.
+            // head(k) rewrites the lane state of scan k - 2: k_wait_final(k - 2) precedes it on this stream, so that
+            // scan is final, and what is left of its tail leaves on tail_gone before touching anything.  The lane's
+            // words count the lane's own scans, which are final in order; between the lanes no order is assumed --
+            // scan k may be final before scan k - 1.  main(k) and main(k - 1) follow each other on this stream.
             launch_correspond_first(c, P0, false);
             if (c->exact) launch_exact_scale_any(c, P, n2, c->stream);
-            if (c->hold_seq != 0) {                       // the previous scan's hold, now behind this scan's head
+            if (overlaps) ++c->overlapped;                // its head went in front of the previous scan's hold
+            if (c->n_hold != 0 && depth <= 1) {        // one scan in flight: that hold now, behind this scan's head
                 const int rcf = flush_hold(c);
                 if (rcf != LO_OK) return rcf;
-                ++c->overlapped;
             }
             for (int it = 0; it < g.max_iterations; ++it) {
                 const bool tail = it >= pipe_main;
                 if (it == pipe_main)                   // bound 0: the test hook's forced timeout
-                    hipLaunchKernelGGL(k_wait_seq, dim3(1), dim3(kWave), 0, c->s_tail, c->d_fin, seq, c->d_st, c->d_hbroken,
-                                       (c->pipe_fail_at != 0 && seq == c->pipe_fail_at) ? 0ull : c->pipe_bound);
-                const hipStream_t s = tail ? c->s_tail : c->stream;
+                    hipLaunchKernelGGL(k_wait_seq, dim3(1), dim3(kWave), 0, s_tail, fin, seq, c->d_st, c->d_hbroken,
+                                       fail ? 0ull : c->pipe_bound);
+                const hipStream_t s = tail ? s_tail : c->stream;
                 const KParams& Pi = tail ? Pt : (it + 1 == pipe_main ? Ph : P);
                 launch_pko_spec(c, Pi, it, s);
                 if (it + 1 < g.max_iterations) hipLaunchKernelGGL(k_pick_correspond, dim3(P.nb), dim3(kBlock), 0, s, Pi, it);
                 else hipLaunchKernelGGL(k_pick, dim3(1), dim3(kBlock), 0, s, Pi, it);
             }
-            if (defer) {                                  // enqueued by the next pipelined scan, or by flush_hold
-                c->hold_seq = seq;
-                c->hold_st = c->d_st;
+            if (defer && c->n_hold < 2) {                 // enqueued by a later pipelined scan, or by flush_hold
+                if (c->n_hold == 0) g_holding.fetch_add(1, std::memory_order_relaxed);
+                c->holds[c->n_hold++] = lo_ctx::Hold{seq, lane, c->d_st};
             } else {
-                hipLaunchKernelGGL(k_wait_final, dim3(1), dim3(kWave), 0, c->stream, c->d_fin, seq, c->d_st, c->d_hbroken,
+                const int rcf = flush_hold(c);            // (none pending: a scan that does not defer flushed them above)
+                if (rcf != LO_OK) return rcf;
+                hipLaunchKernelGGL(k_wait_final, dim3(1), dim3(kWave), 0, c->stream, fin, seq, c->d_st, c->d_hbroken,
                                    c->pipe_bound);
             }
             LO_HIP(c, hipGetLastError());
@@ -566,6 +630,30 @@ int lo_sync(lo_ctx* c) {
 int lo_icp_flush(lo_ctx* c) {
     if (!c) return LO_ERR_ARG;
     return flush_hold(c);
+}
+
+int lo_icp_queue_records(lo_ctx* c, int n_last, float* out16xN) {
+    if (!c || n_last < 0 || (n_last > 0 && !out16xN)) return LO_ERR_ARG;
+    if (n_last > kRingRecords || static_cast<unsigned>(n_last) > c->ring_n) {
+        c->err = "lo_icp_queue_records: n_last exceeds the ring, or the pipelined scans queued since the last other call";
+        return LO_ERR_ARG;
+    }
+    LO_HIP(c, hipSetDevice(c->device));
+    LO_HIP(c, sync_all(c));                              // the holds, then every stream of the context
+    if (pipe_flagged(c)) {                               // a wait timed out: those scans' records were never written
+        const int rc = pipe_recover(c);
+        return rc != LO_OK ? rc : LO_ERR_PIPELINE;
+    }
+    const unsigned long long first = c->ring_pos - static_cast<unsigned long long>(n_last);
+    // oldest first: the run up to the ring's end, then the wrapped rest
+    const size_t slot = static_cast<size_t>(first % kRingRecords);
+    const size_t run = std::min<size_t>(static_cast<size_t>(n_last), kRingRecords - slot);
+    if (run > 0)
+        LO_HIP(c, hipMemcpy(out16xN, c->d_ring + slot * kRecWords, run * kRecWords * sizeof(float), hipMemcpyDeviceToHost));
+    if (run < static_cast<size_t>(n_last))
+        LO_HIP(c, hipMemcpy(out16xN + run * kRecWords, c->d_ring.get(), (n_last - run) * kRecWords * sizeof(float),
+                            hipMemcpyDeviceToHost));
+    return LO_OK;
 }
 
 int lo_icp_optimize(lo_ctx* c, const float* pts, size_t n, const float T_init[12], float T_out[12],

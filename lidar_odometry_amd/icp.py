@@ -151,6 +151,19 @@ class IterativeClosestPointOptimizer:
         if rc != 0:
             raise RuntimeError(f"lo_set_pipeline failed ({rc})")
 
+    def set_scan_depth(self, depth: int = 2):
+        """Queued scans in flight (lo_set_scan_depth): 2 (default) or 1; results are identical either way."""
+        rc = self._L.lo_set_scan_depth(self.ctx, int(depth))
+        if rc != 0:
+            raise RuntimeError(f"lo_set_scan_depth failed ({rc})")
+
+    def queue_records(self, n_last: int) -> np.ndarray:
+        """The records of the last n_last queued pipelined scans, oldest first (lo_icp_queue_records): an
+        (n_last, 16) float32 array of pose[12], status, iterations, n_corr, 0.  Drains the context."""
+        out = np.zeros((int(n_last), 16), np.float32)
+        self._check(self._L.lo_icp_queue_records(self.ctx, int(n_last), _fptr(out)))
+        return out
+
     def close(self):
         h = getattr(self, "_ctx", None)
         if h:
