@@ -199,14 +199,14 @@ int lo_set_pipeline(lo_ctx* ctx, int enable, int main_iterations);
  * CHANGED CONTRACT (default on): two rules that did not exist before this switch --
  *  - work a caller enqueues on a shared stream ITSELF after lo_icp_optimize_async is ordered after the scan's final
  *    result only once lo_icp_flush (or any other library call on the context) has been made;
- *  - the tail of a scan reads its points while the next scan's head runs: the device buffers of the LAST TWO queued
- *    scans must stay valid and unchanged until lo_icp_result (or lo_sync) has returned.  Code that reused or freed a
+ *  - the tail of a scan reads its points while the next scan's head runs: the device buffers of the last queued
+ *    scans -- as many as are in flight: FOUR by default, see SCAN RING below -- must stay valid and unchanged until lo_icp_result (or lo_sync) has returned.  Code that reused or freed a
  *    scan's buffer in stream order right after lo_icp_optimize_async (a tensor handed back to a caching allocator) must
  *    call lo_icp_flush first, or switch the overlap off.
  * NOTE lo_stream: it is a getter that may launch the pending hold (whoever asks for the stream is about to enqueue on
  * it; the device map, the loop detector and the map builder take it this way); poll the handle once, not in a loop.
  * lo_scan_overlap_status: out[0] enabled, out[1] scans whose head was enqueued in front of the previous scan's hold.
- * TWO SCANS IN FLIGHT (lo_set_scan_depth, default 2; LO_OVERLAP_DEPTH=1 in the environment, or depth 1 here, gives the
+ * TWO SCANS IN FLIGHT (lo_set_scan_depth; LO_OVERLAP_DEPTH=1 in the environment, or depth 1 here, gives the
  * one pending hold described above, launch for launch).  With depth 2 a queued scan k enqueues the hold of scan k - 2
  * -- the scan that last used its set of per-scan state -- in front of its own head, and no longer the hold of scan
  * k - 1: up to two holds are pending, each scan's tail has its own stream, and scan k's Gauss-Newton iterations run
@@ -217,11 +217,25 @@ int lo_set_pipeline(lo_ctx* ctx, int enable, int main_iterations);
  * and what is left of that scan's tail leaves before touching its points).  Results are identical for either depth.
  * Unless a depth was chosen here or in the environment, a context keeps ONE scan in flight while other contexts of the
  * process have queued scans in flight: their launches already fill the chip, and more streams only crowd the hardware
- * queues they share.  lo_set_scan_depth: LO_ERR_ARG for a depth other than 1 or 2. */
+ * queues they share.  lo_set_scan_depth: LO_ERR_ARG for a depth other than 1 or 2.
+ * SCAN RING (lo_set_scan_lanes, 1 .. 4; LO_OVERLAP_DEPTH=1 .. 4 in the environment; LO_ERR_ARG outside that range).
+ * lanes = 1 and 2 are lo_set_scan_depth's depths, launch for launch.  With lanes = d >= 3, scan k of a queue runs on
+ * set k % d of the per-scan state, the hold of scan k - d goes in front of its head, and up to d holds are pending.
+ * Unless a split was chosen (lo_set_pipeline with main_iterations >= 1, or LO_PIPE_MAIN; LO_PIPE_MAIN=0 chooses split 0
+ * at any depth), a queued scan then puts ALL its Gauss-Newton iterations on its lane's stream (split 0): the context
+ * stream carries only the hold, the first correspondence launch, the exact scale and a one-wave launch that tells the
+ * lane stream the head is done.  Each lane's set (~1.5 MB at the default max_points) and stream are made when a scan
+ * first runs there.  THE BUFFER RULE SCALES WITH THE DEPTH IN USE: the device buffers of the last d queued scans must
+ * stay valid and unchanged until lo_icp_result (or lo_sync) has returned.  THE DEFAULT IS 4 IN FLIGHT (measured,
+ * DESIGN.md "Scan ring": +27 % queued scans/s over 2; 3 gains 2 %), so by default that is the last FOUR queued scans'
+ * buffers; lo_set_scan_depth(ctx, 2) or LO_OVERLAP_DEPTH=2 gives the former behaviour launch for launch.  The rule for
+ * a process with several contexts queueing scans (one in flight each unless chosen) is unchanged.  Results are
+ * identical for every value. */
 int lo_set_scan_overlap(lo_ctx* ctx, int enable);
 int lo_scan_overlap_status(lo_ctx* ctx, long long out[2]);
 int lo_set_scan_depth(lo_ctx* ctx, int depth);
-/* Enqueue the pending holds of the last queued scans (at most two) on the context stream now, oldest first (no-op when
+int lo_set_scan_lanes(lo_ctx* ctx, int lanes);
+/* Enqueue the pending holds of the last queued scans (at most the depth in use) on the context stream now, oldest first (no-op when
  * there is none): what follows on that stream sees those scans' final results.  Does not wait on the host. */
 int lo_icp_flush(lo_ctx* ctx);
 /* Every queued scan's record, not only the last one's.  Each pipelined scan (a small surfel scan with PKO while the
@@ -250,7 +264,7 @@ int lo_set_pko_groups(lo_ctx* ctx, int groups);
  * the points of the context's LAST enqueued scan again: after lo_icp_optimize_async / lo_icp_optimize_raw_async the
  * caller's device buffer (d_pts / d_raw, and the device count) must therefore stay valid and unchanged until
  * lo_icp_result has returned -- the same lifetime a stream-ordered reader of the buffer needs anyway (with scan
- * overlap, the last TWO queued scans' buffers: see lo_set_scan_overlap).  Earlier async scans are never re-run: their
+ * overlap, the buffers of as many last queued scans as are in flight, four by default: see lo_set_scan_overlap).  Earlier async scans are never re-run: their
  * exported records keep LO_ERR_PIPELINE. */
 int lo_pipeline_status(lo_ctx* ctx, int out[4]);
 /* In-step timing: with enable, each optimize brackets its FIRST correspondence launch (k_correspond, or the KDTree

@@ -8,7 +8,7 @@
 
 namespace lo {
 // All streams of the context drained (lo_sync, lo_set_stream, lo_destroy): the pending holds first, then the context
-// stream and both lanes' tail streams.
+// stream and every lane's tail stream.
 hipError_t sync_all(lo_ctx* c) {
     if (c->stream && flush_hold(c) != LO_OK) return hipErrorUnknown;   // (the text is in c->err)
     hipError_t e = c->stream ? hipStreamSynchronize(c->stream) : hipSuccess;
@@ -216,9 +216,14 @@ lo_ctx* lo_create(const lo_config* cfg, int device, int* err) {
         if (*cc && std::strcmp(cc, "0") != 0 && std::strcmp(cc, "False") != 0 && std::strcmp(cc, "false") != 0) c->pipe = false;
     }
     if (const char* pp = std::getenv("LO_PIPE")) c->pipe = std::atoi(pp) != 0;
-    if (const char* pm = std::getenv("LO_PIPE_MAIN")) { c->pipe_main = std::max(1, std::atoi(pm)); c->pipe_main_auto = false; }
+    // (0: split 0, every GN iteration of a scan on its lane's stream)
+    if (const char* pm = std::getenv("LO_PIPE_MAIN")) { c->pipe_main = std::max(0, std::atoi(pm)); c->pipe_main_auto = false; }
     if (const char* po = std::getenv("LO_OVERLAP")) c->overlap = std::atoi(po) != 0;
-    if (const char* pd = std::getenv("LO_OVERLAP_DEPTH")) { c->depth = std::atoi(pd) <= 1 ? 1 : 2; c->depth_auto = false; }
+    if (const char* pd = std::getenv("LO_OVERLAP_DEPTH")) {
+        c->depth = std::min(std::max(std::atoi(pd), 1), kMaxLanes);
+        c->depth_auto = false;
+    }
+    c->depth_used = c->depth;
     if (const char* pw = std::getenv("LO_PIPE_WAIT_MS")) c->pipe_bound = 100000ull * std::max(1, std::atoi(pw));
     if (const char* pf = std::getenv("LO_PIPE_FAIL_AT")) c->pipe_fail_at = static_cast<uint32_t>(std::max(0, std::atoi(pf)));
     if (const char* pg = std::getenv("LO_PKO_GROUPS")) c->pko_groups = std::max(0, std::atoi(pg));
@@ -286,12 +291,16 @@ int lo_update_config(lo_ctx* c, const lo_config* cfg) {
     c->cfg = *cfg;
     ++c->cfg_gen;                                        // batches re-upload this context's parameters
     if (na_changed || (cfg->use_adaptive_m_estimator && !c->d_acc_part)) {
-        // the candidate buffers are sized by the alpha grid: re-made on the next optimize (the second lane whole)
+        // the candidate buffers are sized by the alpha grid: re-made on the next optimize (the other lanes whole)
         c->d_acc_part.reset();
         c->d_cand_rec.reset();
         c->d_cand_cnt.reset();
-        c->alt = lo_ctx::ScanLane{};
-        c->alt_ready = false;
+        for (int l = 0; l < kMaxLanes; ++l) {
+            if (l == c->lane) continue;
+            c->lanes[l] = lo_ctx::ScanLane{};
+            c->lane_ready[l] = false;
+        }
+        c->prev_lane = -1;
     }
     return LO_OK;
 }
@@ -343,6 +352,17 @@ int lo_set_scan_depth(lo_ctx* c, int depth) {
     const int rc = flush_hold(c);
     if (rc != LO_OK) return rc;
     c->depth = depth;
+    c->depth_auto = false;
+    return LO_OK;
+}
+
+// The scan ring: up to kMaxLanes queued scans in flight, scan k of a queue on lane k % lanes.  1 and 2 are
+// lo_set_scan_depth's; from 3 on a queue's scans take split 0 unless a split was chosen (enqueue_optimize).
+int lo_set_scan_lanes(lo_ctx* c, int lanes) {
+    if (!c || lanes < 1 || lanes > kMaxLanes) return LO_ERR_ARG;
+    const int rc = flush_hold(c);
+    if (rc != LO_OK) return rc;
+    c->depth = lanes;
     c->depth_auto = false;
     return LO_OK;
 }

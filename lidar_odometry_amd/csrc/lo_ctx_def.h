@@ -176,13 +176,15 @@ struct lo_ctx {
     int pko_groups = 0;             // EM workgroups per PKO launch (lo_set_pko_groups / LO_PKO_GROUPS; 0 = one per alpha)
     bool pko_solo = false;          // LO_PKO_SOLO=1 (A/B): the speculative PKO launch asks for enough LDS that one
                                     //   workgroup holds a CU alone (no other launch's waves on its SIMDs)
-    hipStream_t s_tail[2] = {nullptr, nullptr};   // one tail stream per lane (scan overlap, below): a scan's tail does not
-                                    //   queue behind the early-exit launches of the other lane's scan
+    static constexpr int kMaxLanes = 4;             // sets of per-scan state, and queued scans in flight at most (scan ring)
+    hipStream_t s_tail[kMaxLanes] = {};   // one tail stream per lane (scan overlap, below), made when a scan first runs
+                                    //   there: a scan's tail does not queue behind the early-exit launches of another lane's
     uint32_t pipe_seq = 0;          // pipelined scans so far (LO_PIPE_FAIL_AT counts in it)
-    uint32_t lane_seq[2] = {0, 0};  // each lane's own sequence number: what its fence words count in (never 0)
-    DevBuf<uint32_t> d_fin;         // kFinWords per lane (KParams::fin names the lane's group): [0] the lane's last scan
-                                    // whose result is final (publish_final), [1] main part done, [2] signal_main's block
-                                    // count, [3] broken (a wait timed out; sticky, and set in both groups: pipe_fail)
+    uint32_t lane_seq[kMaxLanes] = {};   // each lane's own sequence number: what its fence words count in (never 0)
+    DevBuf<uint32_t> d_fin;         // kFinWords per lane, kMaxLanes groups (KParams::fin names the lane's group): [0] the
+                                    // lane's last scan whose result is final (publish_final), [1] main part done, [2]
+                                    // signal_main's block count, [3] broken (a wait timed out; sticky, and set in every
+                                    // group: pipe_fail)
     MappedBuf<uint32_t> h_broken;   // device-mapped: the seq of the scan whose wait timed out (0: none)
     uint32_t* d_hbroken = nullptr;  //   its device alias (not owned)
     unsigned long long pipe_bound = 200000000ull;   // wait bound in 100 MHz ticks (2 s; LO_PIPE_WAIT_MS)
@@ -197,6 +199,9 @@ struct lo_ctx {
     // while another is in flight), and lane_switch swaps them.  Every other entry point that touches the context stream
     // or a queued scan's inputs enqueues the pending hold first (flush_hold), after which the context is as it was
     // before this existed.  The map and the PKO tables are shared; each lane has its own fence words and tail stream.
+    // Scan ring (lo_set_scan_lanes): up to kMaxLanes such sets.  `lanes[i]` holds lane i's set while another lane is the
+    // current one (the current lane's entry is empty: its set is the members above); a set is allocated the first time
+    // a scan runs on its lane, so a context that never queues scans pays for none (~1.5 MB each at the default max_points).
     struct ScanLane {
         DevBuf<int32_t> d_slot;
         DevBuf<double> d_res_pko;
@@ -208,23 +213,28 @@ struct lo_ctx {
         DevBuf<double> d_js;
         DevBuf<DevState> d_st;
     };
-    ScanLane alt;
-    bool alt_ready = false;         // alt holds a full set, its candidate buffers sized for the current alpha grid
-    int lane = 0;                   // which set the members above are (scan k of an overlapped run: k & 1)
+    ScanLane lanes[kMaxLanes];
+    bool lane_ready[kMaxLanes] = {true, false, false, false};   // lane i has a full set (in lanes[i], or the members when
+                                    //   it is the current one), its candidate buffers sized for the current alpha grid
+    int lane = 0;                   // which set the members above are (scan k of a queue: k % max(depth, 2))
+    int prev_lane = -1;             // the lane the last switch left: the scan enqueued before the last one ran there
+                                    //   (lo_debug_other_lane_record; -1: no scan has overlapped yet)
     bool overlap = true;
-    // Two scans in flight (lo_set_scan_depth; depth 2 by default, LO_OVERLAP_DEPTH=1 for one): the hold of scan k - 1 is
-    // no longer enqueued by scan k, only the hold of scan k - 2 -- the scan that last used scan k's lane -- and in front
-    // of scan k's head.  So up to `depth` holds are pending, and scan k's GN iterations run beside scan k - 1's tail.
+    // `depth` >= 2 scans in flight (lo_set_scan_depth / lo_set_scan_lanes / LO_OVERLAP_DEPTH): the hold of scan k - 1 is
+    // no longer enqueued by scan k, only the hold of scan k - depth -- the scan that last used scan k's lane -- and in
+    // front of scan k's head.  So up to `depth` holds are pending, and scan k's GN iterations run beside scan k - 1's tail.
+    static constexpr int kDefaultDepth = 4;         // queued scans in flight unless chosen: 4 with split 0 measured +27 % over
+                                                    //   2, and 3 only +2 % (DESIGN.md "Scan ring")
     struct Hold {
         uint32_t seq;               // the scan's number on its lane
         int lane;
         DevState* st;               // its lane's DevState (a timed-out wait marks it LO_ERR_PIPELINE)
     };
-    Hold holds[2];                  // the scans whose k_wait_final is still to be enqueued, oldest first
+    Hold holds[kMaxLanes];          // the scans whose k_wait_final is still to be enqueued, oldest first
     int n_hold = 0;
-    int depth = 2;
+    int depth = kDefaultDepth;
     bool depth_auto = true;         // no depth chosen: one scan in flight while other contexts queue scans too (scan_depth)
-    int depth_used = 2;             // the depth the pending holds were placed for
+    int depth_used = kDefaultDepth; // the depth the pending holds were placed for
     // every pipelined scan's 16-float record (lo_icp_queue_records): the thread that publishes a scan final writes it
     DevBuf<float> d_ring;           // kRingRecords x 16 floats
     unsigned long long ring_pos = 0;   // pipelined scans given a slot so far (slot = ring_pos % kRingRecords)
@@ -239,6 +249,8 @@ struct lo_ctx {
 namespace lo {
 constexpr int kStageEvents = 1024;
 constexpr int kFinWords = 4;                          // fence words per lane (lo_ctx::d_fin; pipe_fail relies on the 4)
+constexpr int kMaxLanes = lo_ctx::kMaxLanes;          // (pipe_fail writes every group of the block)
+static_assert(kMaxLanes == kFinLanes && kFinWords == 4, "pipe_fail masks a fence-word address to the block of all lanes");
 constexpr int kRingRecords = 64;                      // lo_icp_queue_records: records kept per context
 constexpr int kRecWords = 16;                         //   floats per record (lo_icp_export_pose's layout)
 constexpr int kExactMaxPoints = 16384;                // reference-exact mode: one-workgroup sort in LDS up to here

@@ -182,6 +182,7 @@ struct KParams {
 // Scan pipeline: poll a flag word until it reaches seq (one lane, sc1 loads: fresh across XCDs; the word is the only
 // thing read), bounded by `bound` ticks of the 100 MHz constant clock -- false on timeout, so no wait can hang a queue.
 // A wait also gives up at once when the pipeline is broken (fin[3] != 0: an earlier wait timed out).
+constexpr int kFinLanes = 4;      // groups of four fence words in a context's block (lo_ctx::kMaxLanes; pipe_fail)
 __device__ __forceinline__ bool wait_word(const uint32_t* w, uint32_t seq, const uint32_t* broken, unsigned long long bound) {
     const unsigned long long t0 = wall_clock64();
     while (static_cast<int32_t>(__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - seq) < 0) {

@@ -460,14 +460,17 @@ int lo_debug_cand_records(lo_ctx* c, float* out, size_t cap_words) {
 }
 
 // The 16-float record (as lo_icp_export_pose) of the scan on the OTHER lane: the scan queued before the last one, whose
-// tail ran beside the last scan's head (scan overlap).  Drains both streams first.
+// tail ran beside the last scan's head (scan overlap) -- whichever lane of the ring that was.  Drains every stream first.
 int lo_debug_other_lane_record(lo_ctx* c, float out16[16]) {
     if (!c || !out16) return LO_ERR_ARG;
     LO_HIP(c, hipSetDevice(c->device));
     LO_HIP(c, sync_all(c));
-    if (!c->alt_ready) { c->err = "lo_debug_other_lane_record: no scan has overlapped yet"; return LO_ERR_STATE; }
+    if (c->prev_lane < 0 || !c->lanes[c->prev_lane].d_st) {
+        c->err = "lo_debug_other_lane_record: no scan has overlapped yet";
+        return LO_ERR_STATE;
+    }
     std::vector<char> h(offsetof(DevState, logs));
-    LO_HIP(c, hipMemcpy(h.data(), c->alt.d_st.get(), h.size(), hipMemcpyDeviceToHost));
+    LO_HIP(c, hipMemcpy(h.data(), c->lanes[c->prev_lane].d_st.get(), h.size(), hipMemcpyDeviceToHost));
     const DevState* st = reinterpret_cast<const DevState*>(h.data());   // (header fields only)
     for (int k = 0; k < 12; ++k) out16[k] = st->pose[k];
     out16[12] = static_cast<float>(st->status);

@@ -478,12 +478,21 @@ __global__ void k_init(DevState* st, Pose12 T, double scale, double alpha) {
 // the pipeline off at its next enqueue and re-runs a synchronous call's scan on one stream).
 __device__ __forceinline__ void pipe_fail(uint32_t* fin, uint32_t* hbroken, uint32_t seq, DevState* st) {
     st->status = LO_ERR_PIPELINE;
-    // fin is one lane's group of four words; the two groups lie side by side in one 32-byte aligned block (lo_ctx::d_fin),
-    // and the broken word is set in both: a wait that timed out on either lane stops both
-    uint32_t* both = reinterpret_cast<uint32_t*>(reinterpret_cast<uintptr_t>(fin) & ~static_cast<uintptr_t>(31));
-    __hip_atomic_store(both + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(both + 7, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // fin is one lane's group of four words; the kFinLanes groups lie side by side in one aligned block of kFinLanes x
+    // 16 bytes (lo_ctx::d_fin), and the broken word is set in every group: a wait that timed out on any lane stops all
+    uint32_t* all = reinterpret_cast<uint32_t*>(reinterpret_cast<uintptr_t>(fin) & ~static_cast<uintptr_t>(kFinLanes * 16 - 1));
+#pragma unroll
+    for (int l = 0; l < kFinLanes; ++l) __hip_atomic_store(all + 4 * l + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (hbroken) __hip_atomic_store(hbroken, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// Split 0 (every GN iteration of the scan on its lane's stream): the launch behind the scan's head on the context
+// stream.  The head's kernels have ended, their stores are out; this sets the lane's "main part done" word that
+// k_wait_seq polls (release first, as signal_main does).  Nothing here waits.
+__global__ void k_signal_main(uint32_t* fin, uint32_t seq) {
+    if (threadIdx.x != 0) return;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __hip_atomic_store(fin + 1, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __global__ void k_wait_seq(uint32_t* fin, uint32_t seq, DevState* st, uint32_t* hbroken, unsigned long long bound) {
     if (threadIdx.x != 0) return;

@@ -24,6 +24,7 @@ __global__ void k_init(DevState* st, Pose12 T, double scale, double alpha);
 __global__ void k_export_pose(const DevState* st, float* out);
 __global__ void k_wait_seq(uint32_t* fin, uint32_t seq, DevState* st, uint32_t* hbroken, unsigned long long bound);
 __global__ void k_wait_final(uint32_t* fin, uint32_t seq, DevState* st, uint32_t* hbroken, unsigned long long bound);
+__global__ void k_signal_main(uint32_t* fin, uint32_t seq);
 __global__ void k_knn(KParams P);
 __global__ void k_knn_brute(KParams P);
 __global__ void k_knn_brute_w(KParams P);

@@ -57,10 +57,11 @@ static void launch_gn_tail(lo_ctx* c, const KParams& P, int it) {
 // Scan pipeline (first pipelined scan): the lanes' tail streams, their fence words, the record ring, the host flag.
 static int pipe_alloc(lo_ctx* c) {
     if (c->d_hbroken) return LO_OK;                 // set last
-    // (the first lane's tail stream; the second lane's is made when a scan first runs there with two in flight)
+    // (the first lane's tail stream; another lane's is made when a scan first runs there with two or more in flight)
     if (!c->s_tail[0]) LO_HIP(c, hipStreamCreateWithFlags(&c->s_tail[0], hipStreamNonBlocking));
-    LO_HIP(c, c->d_fin.reserve(2 * kFinWords));     // (pipe_fail finds both groups from either: 32 bytes, aligned)
-    LO_HIP(c, hipMemset(c->d_fin, 0, 2 * kFinWords * sizeof(uint32_t)));
+    // (pipe_fail finds every group from any one: kMaxLanes x 16 bytes, aligned to that -- hipMalloc aligns to 256)
+    LO_HIP(c, c->d_fin.reserve(kMaxLanes * kFinWords));
+    LO_HIP(c, hipMemset(c->d_fin, 0, kMaxLanes * kFinWords * sizeof(uint32_t)));
     LO_HIP(c, c->d_ring.reserve(static_cast<size_t>(kRingRecords) * kRecWords));
     LO_HIP(c, hipMemset(c->d_ring, 0, static_cast<size_t>(kRingRecords) * kRecWords * sizeof(float)));
     LO_HIP(c, c->h_broken.reserve(1));
@@ -70,18 +71,19 @@ static int pipe_alloc(lo_ctx* c) {
     return LO_OK;
 }
 
-// A pipeline wait timed out (the dispatcher ran the streams out of submission order): drain all three streams, switch
-// the pipeline off for this context, clear the flag words.  Scans enqueued before this point report LO_ERR_PIPELINE
-// (their tails left without touching anything); a synchronous call re-runs its scan on one stream (lo_icp_result).
+// A pipeline wait timed out (the dispatcher ran the streams out of submission order): drain the context stream and every
+// lane stream, switch the pipeline off for this context, clear the flag words.  Scans enqueued before this point report
+// LO_ERR_PIPELINE (their tails left without touching anything); a synchronous call re-runs its scan on one stream
+// (lo_icp_result).
 static int pipe_recover(lo_ctx* c) {
-    LO_HIP(c, sync_all(c));                         // (enqueues the pending holds of both lanes first: they give up at once)
+    LO_HIP(c, sync_all(c));                         // (enqueues the pending holds of every lane first: they give up at once)
     c->pipe = false;
     ++c->pipe_timeouts;
     c->ring_n = 0;                                  // (the records of the scans that gave up were never written)
     c->err = "scan pipeline: a device-side wait timed out (the streams were not run concurrently, e.g. rocprofv3 "
              "counter collection); pipeline switched off for this context";
-    LO_HIP(c, hipMemset(c->d_fin, 0, 2 * kFinWords * sizeof(uint32_t)));
-    c->lane_seq[0] = c->lane_seq[1] = 0;            // (with the words they count in)
+    LO_HIP(c, hipMemset(c->d_fin, 0, kMaxLanes * kFinWords * sizeof(uint32_t)));
+    for (uint32_t& s : c->lane_seq) s = 0;          // (with the words they count in)
     LO_HIP(c, hipStreamSynchronize(nullptr));
     __atomic_store_n(c->h_broken.get(), 0u, __ATOMIC_RELEASE);
     return LO_OK;
@@ -95,7 +97,7 @@ static std::atomic<int> g_holding{0};
 // the held scan's own DevState (its lane's) LO_ERR_PIPELINE.
 static int pop_hold(lo_ctx* c) {
     const lo_ctx::Hold h = c->holds[0];
-    c->holds[0] = c->holds[1];
+    for (int i = 1; i < c->n_hold; ++i) c->holds[i - 1] = c->holds[i];
     if (--c->n_hold == 0) g_holding.fetch_sub(1, std::memory_order_relaxed);
     LO_HIP(c, hipSetDevice(c->device));
     hipLaunchKernelGGL(k_wait_final, dim3(1), dim3(kWave), 0, c->stream, c->d_fin + kFinWords * h.lane, h.seq, h.st,
@@ -139,12 +141,28 @@ static bool pipelined_scan(const lo_ctx* c, bool cand, int pipe_main) {
     return cand && !c->kd && c->pipe && c->cfg.max_iterations > pipe_main;
 }
 
-// The second lane: a full set of the per-scan state (same sizes as ctx_alloc's and ensure_acc_part's), then the swap.
+// The context's members <-> a lane's set
+static void lane_swap(lo_ctx* c, lo_ctx::ScanLane& A) {
+    std::swap(A.d_slot, c->d_slot);
+    std::swap(A.d_res_pko, c->d_res_pko);
+    std::swap(A.d_wmask, c->d_wmask);
+    std::swap(A.d_blk_cnt, c->d_blk_cnt);
+    std::swap(A.d_blk_sum, c->d_blk_sum);
+    std::swap(A.d_blk_m2, c->d_blk_m2);
+    std::swap(A.d_blk_part, c->d_blk_part);
+    std::swap(A.d_acc_part, c->d_acc_part);
+    std::swap(A.d_cand_rec, c->d_cand_rec);
+    std::swap(A.d_cand_cnt, c->d_cand_cnt);
+    std::swap(A.d_js, c->d_js);
+    std::swap(A.d_st, c->d_st);
+}
+// Lane `to` becomes the current one: a full set of the per-scan state on its first use (same sizes as ctx_alloc's and
+// ensure_acc_part's), then the current set is parked in its own entry and lane `to`'s taken out of its entry.
 // Depth 1: nothing of the lane swapped in is in flight, its last scan's hold was enqueued before the scan now pending
-// started.  Depth 2: that hold may still be pending, and the caller enqueues it before anything touches the lane.
-static int lane_switch(lo_ctx* c) {
-    lo_ctx::ScanLane& A = c->alt;
-    if (!c->alt_ready) {
+// started.  Depth >= 2: that hold may still be pending, and the caller enqueues it before anything touches the lane.
+static int lane_switch(lo_ctx* c, int to) {
+    lo_ctx::ScanLane& A = c->lanes[to];
+    if (!c->lane_ready[to]) {
         const lo_config& g = c->cfg;
         const size_t NB = (static_cast<size_t>(g.max_points) + kBlock - 1) / kBlock;
         const size_t cand = static_cast<size_t>(g.num_alpha_segments) + 1;
@@ -163,21 +181,11 @@ static int lane_switch(lo_ctx* c) {
         // zeroed on the context stream: this scan's head follows there, and its tail starts only behind its main part
         LO_HIP(c, hipMemsetAsync(A.d_cand_cnt, 0, cand * sizeof(unsigned), c->stream));
         LO_HIP(c, A.d_acc_part.reserve(cand * kFuseMaxBlocks * kNE));
-        c->alt_ready = true;
+        c->lane_ready[to] = true;
     }
-    std::swap(A.d_slot, c->d_slot);
-    std::swap(A.d_res_pko, c->d_res_pko);
-    std::swap(A.d_wmask, c->d_wmask);
-    std::swap(A.d_blk_cnt, c->d_blk_cnt);
-    std::swap(A.d_blk_sum, c->d_blk_sum);
-    std::swap(A.d_blk_m2, c->d_blk_m2);
-    std::swap(A.d_blk_part, c->d_blk_part);
-    std::swap(A.d_acc_part, c->d_acc_part);
-    std::swap(A.d_cand_rec, c->d_cand_rec);
-    std::swap(A.d_cand_cnt, c->d_cand_cnt);
-    std::swap(A.d_js, c->d_js);
-    std::swap(A.d_st, c->d_st);
-    c->lane ^= 1;
+    lane_swap(c, c->lanes[c->lane]);                    // (that entry was empty: the members are now)
+    lane_swap(c, A);
+    c->lane = to;
     ++c->cfg_gen;                                       // a batch's cached device KParams name the other lane's buffers
     return LO_OK;
 }
@@ -372,24 +380,33 @@ int enqueue_optimize(lo_ctx* c, const float* d_pts, size_t n, const float T_init
     // (pipe_main, 1 by default): the caller is queueing scans back to back, and the next head hides under a longer tail.
     // A scan behind a flushed hold (its caller read the previous result, or made any other call) keeps the split 2 a
     // scan always had unless one was chosen -- split 1 without overlap costs about 1 %.
-    const bool overlaps = c->n_hold != 0 && may_defer && pipelined_scan(c, cand, c->pipe_main);
-    const int pipe_main = (c->pipe_main_auto && !overlaps) ? 2 : c->pipe_main;
+    // Three or more in flight and no split chosen: the queue's split is 0 -- every GN iteration of an overlapping scan
+    // runs on its lane's stream, and the context stream carries only the heads and the holds (DESIGN.md "Scan ring").
+    const int queue_main = (c->pipe_main_auto && depth >= 3) ? 0 : c->pipe_main;
+    const bool overlaps = c->n_hold != 0 && may_defer && pipelined_scan(c, cand, queue_main);
+    const int pipe_main = (c->pipe_main_auto && !overlaps) ? 2 : queue_main;
     const bool defer = may_defer && pipelined_scan(c, cand, pipe_main);
+    const int lane_before = c->lane;
     if (c->n_hold != 0) {
         if (!overlaps) {                                  // any other path: the context as it always was
             const int rcf = flush_hold(c);
             if (rcf != LO_OK) return rcf;
-        } else {                                          // this scan's state goes to the other lane
-            const int rcl = lane_switch(c);
+        } else {                                          // this scan's state goes to the next lane of the ring
+            const int rcl = lane_switch(c, (c->lane + 1) % std::max(depth, 2));
             if (rcl != LO_OK) return rcl;
-            // ... which the scan before the previous one used.  Two scans in flight: its hold is still pending, and
-            // goes in front of this scan's head, which rewrites the state that scan's tail reads.
-            if (depth > 1 && c->holds[0].lane == c->lane) {
+            // ... which scan k - depth used.  Two or more in flight: its hold may still be pending (with every older
+            // one), and goes in front of this scan's head, which rewrites the state that scan's tail reads.
+            // (Never more than `depth` in flight either, whatever lanes an earlier depth left the holds on.)
+            int pops = c->n_hold - depth + 1;
+            for (int i = 0; i < c->n_hold; ++i)
+                if (c->holds[i].lane == c->lane) pops = std::max(pops, i + 1);
+            for (int i = 0; depth > 1 && i < pops; ++i) {
                 const int rch = pop_hold(c);
                 if (rch != LO_OK) return rch;
             }
         }
     }
+    if (c->lane != lane_before) c->prev_lane = lane_before;
     if (timed) LO_HIP(c, hipEventRecord(c->ev0, c->stream));
     if (n == 0) {
         hipLaunchKernelGGL(k_init, dim3(1), dim3(64), 0, c->stream, c->d_st, T0, 1.0, g.robust_loss_delta);
@@ -459,23 +476,31 @@ int enqueue_optimize(lo_ctx* c, const float* d_pts, size_t n, const float T_init
             Pt.tail = 1;                                  // DevState may already be the next scan's)
             KParams Ph = P;                               // the main part's last pick signals the tail (signal_main)
             Ph.hold = 1;
-            // host submission order of a queue of scans, scan k on lane k & 1 (two in flight, the default):
-            //   context stream:   k_wait_final(k - 2) -> head(k) -> main(k)        (the wait was placed above)
-            //   tail stream k & 1: k_wait_seq(k) -> tail(k)
-            // and k_wait_final(k) is placed by scan k + 2, or by flush_hold.  With one scan in flight (depth 1) the
-            // context stream carries head(k) -> k_wait_final(k - 1) -> main(k) instead.
+            // host submission order of a queue of scans with d = depth >= 2 in flight, scan k on lane k % d:
+            //   context stream:     k_wait_final(k - d) -> head(k) -> main(k)     (the wait was placed above)
+            //   lane stream k % d:  k_wait_seq(k) -> tail(k)
+            // and k_wait_final(k) is placed by scan k + d, or by flush_hold.  main(k) is the iterations below the split:
+            // with split 0 (the queue's split from three in flight on) there is none, the context stream carries
+            // k_wait_final(k - d) -> head(k) -> k_signal_main(k), and every iteration is tail(k).  With one scan in
+            // flight (depth 1) the context stream carries head(k) -> k_wait_final(k - 1) -> main(k) instead.
             // Every device-side wait depends only on work submitted before it, on any stream: k_wait_final(j) polls
             // the lane's word that main(j) or tail(j) publishes, both submitted during scan j's own call, which
             // returned before any call that can place that wait; k_wait_seq(k) polls the lane's word that main(k)'s
-            // last pick sets, submitted just above it, or the one main(k) publishes when it ends the scan.  Nothing
-            // waits for a later submission, so the order is deadlock-free even if all three streams share one hardware
-            // queue (they then simply run in this order), and every wait is bounded by pipe_bound besides.
-            // head(k) rewrites the lane state of scan k - 2: k_wait_final(k - 2) precedes it on this stream, so that
+            // last pick sets -- with split 0 the one k_signal_main(k) sets behind head(k) -- submitted just above it,
+            // or the one main(k) publishes when it ends the scan.  Nothing waits for a later submission, so the order
+            // is deadlock-free even if all the streams share one hardware queue (they then simply run in this order),
+            // and every wait is bounded by pipe_bound besides.
+            // head(k) rewrites the lane state of scan k - d: k_wait_final(k - d) precedes it on this stream, so that
             // scan is final, and what is left of its tail leaves on tail_gone before touching anything.  The lane's
             // words count the lane's own scans, which are final in order; between the lanes no order is assumed --
-            // scan k may be final before scan k - 1.  main(k) and main(k - 1) follow each other on this stream.
+            // scan k may be final before scan k - 1.  main(k) and main(k - 1) follow each other on this stream; with
+            // split 0 tail(k) and tail(k - 1) share nothing but the map and the tables, which neither writes.
             launch_correspond_first(c, P0, false);
             if (c->exact) launch_exact_scale_any(c, P, n2, c->stream);
+            // split 0: no pick of a main part to say so -- "head done" is one more launch behind the head (the head's
+            // stores are out when it starts; it releases and sets the lane's word).  The context stream is not the
+            // bound once the iterations have left it.
+            if (pipe_main == 0) hipLaunchKernelGGL(k_signal_main, dim3(1), dim3(kWave), 0, c->stream, fin, seq);
             if (overlaps) ++c->overlapped;                // its head went in front of the previous scan's hold
             if (c->n_hold != 0 && depth <= 1) {        // one scan in flight: that hold now, behind this scan's head
                 const int rcf = flush_hold(c);
@@ -492,7 +517,7 @@ int enqueue_optimize(lo_ctx* c, const float* d_pts, size_t n, const float T_init
                 if (it + 1 < g.max_iterations) hipLaunchKernelGGL(k_pick_correspond, dim3(P.nb), dim3(kBlock), 0, s, Pi, it);
                 else hipLaunchKernelGGL(k_pick, dim3(1), dim3(kBlock), 0, s, Pi, it);
             }
-            if (defer && c->n_hold < 2) {                 // enqueued by a later pipelined scan, or by flush_hold
+            if (defer && c->n_hold < kMaxLanes) {         // enqueued by a later pipelined scan, or by flush_hold
                 if (c->n_hold == 0) g_holding.fetch_add(1, std::memory_order_relaxed);
                 c->holds[c->n_hold++] = lo_ctx::Hold{seq, lane, c->d_st};
             } else {

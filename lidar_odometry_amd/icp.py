@@ -157,6 +157,14 @@ class IterativeClosestPointOptimizer:
         if rc != 0:
             raise RuntimeError(f"lo_set_scan_depth failed ({rc})")
 
+    def set_scan_lanes(self, lanes: int = 2):
+        """Queued scans in flight, 1 to 4 (lo_set_scan_lanes): 1 and 2 are set_scan_depth's; from 3 on a queued scan runs
+        all its GN iterations on its lane's stream.  The device buffers of the last `lanes` queued scans must stay valid
+        until the result is read.  Results are identical for every value."""
+        rc = self._L.lo_set_scan_lanes(self.ctx, int(lanes))
+        if rc != 0:
+            raise RuntimeError(f"lo_set_scan_lanes failed ({rc})")
+
     def queue_records(self, n_last: int) -> np.ndarray:
         """The records of the last n_last queued pipelined scans, oldest first (lo_icp_queue_records): an
         (n_last, 16) float32 array of pose[12], status, iterations, n_corr, 0.  Drains the context."""
