@@ -381,11 +381,11 @@ int lo_batch_optimize_async(lo_batch* b, const float* const* d_pts, const size_t
             lo_ctx* c = b->ctx[j];
             const float* pts = (d_pts && d_pts[j]) ? d_pts[j] : c->d_pts;
             LO_HIP(b, hipStreamWaitEvent(c->stream, b->ev_go, 0));
-            const bool pipe = c->pipe, sync_call = c->sync_call;
-            c->pipe = false;
+            const bool pipe = c->q.pipe, sync_call = c->sync_call;
+            c->q.pipe = false;
             c->sync_call = false;
             const int rc = enqueue_optimize(c, pts, n[j], T_init + 12 * j);
-            c->pipe = pipe;
+            c->q.pipe = pipe;
             c->sync_call = sync_call;
             c->pending = false;                               // the batch collects the record, not lo_icp_result
             if (rc != LO_OK) { b->err = std::string("exact job: ") + c->err; return rc; }
@@ -456,11 +456,11 @@ int lo_batch_result(lo_batch* b, lo_batch_rec* out, double* gpu_ms) {
             // points are still the caller's), and the record of that run
             int rc = grid_add_order(c);
             if (rc != LO_OK) { b->err = std::string("tie re-run: ") + c->err; return rc; }
-            const bool pipe = c->pipe, sync_call = c->sync_call;
-            c->pipe = false;
+            const bool pipe = c->q.pipe, sync_call = c->sync_call;
+            c->q.pipe = false;
             c->sync_call = false;
             rc = enqueue_optimize(c, b->act_pts[a], b->n[j], b->T_in.data() + 12 * j);
-            c->pipe = pipe;
+            c->q.pipe = pipe;
             c->sync_call = sync_call;
             c->pending = false;
             if (rc != LO_OK) { b->err = std::string("tie re-run: ") + c->err; return rc; }

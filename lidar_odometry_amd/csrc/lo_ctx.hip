@@ -12,7 +12,7 @@ namespace lo {
 hipError_t sync_all(lo_ctx* c) {
     if (c->stream && flush_hold(c) != LO_OK) return hipErrorUnknown;   // (the text is in c->err)
     hipError_t e = c->stream ? hipStreamSynchronize(c->stream) : hipSuccess;
-    for (hipStream_t s : c->s_tail)
+    for (hipStream_t s : c->q.s_tail)
         if (e == hipSuccess && s) e = hipStreamSynchronize(s);
     return e;
 }
@@ -152,22 +152,14 @@ static int ctx_alloc(lo_ctx* c) {
     LO_HIP(c, hipSetDevice(c->device));
     LO_HIP(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     const size_t N = static_cast<size_t>(g.max_points);
-    const size_t NB = (N + kBlock - 1) / kBlock;
     LO_HIP(c, c->d_pts.reserve(N * 3));
-    LO_HIP(c, c->d_slot.reserve(NB * kBlock));
-    LO_HIP(c, c->d_res_pko.reserve(NB * kBlock));
-    LO_HIP(c, c->d_wmask.reserve(NB * kWavesPerBlock));
-    LO_HIP(c, c->d_blk_cnt.reserve(NB));
-    LO_HIP(c, c->d_blk_sum.reserve(NB));
-    LO_HIP(c, c->d_blk_m2.reserve(NB));
-    LO_HIP(c, c->d_blk_part.reserve(NB * kNE));
-    LO_HIP(c, c->d_js.reserve(kMaxAlpha + 1));
-    LO_HIP(c, c->d_st.reserve(1));
+    const int rc_l = lane_alloc_base(c, cur(c));         // (lane 0; its candidate buffers: ensure_acc_part)
+    if (rc_l != LO_OK) return rc_l;
     LO_HIP(c, c->h_st.reserve(1));
     std::memset(c->h_st, 0, sizeof(DevState));
     LO_HIP(c, c->h_nf.reserve(1));
     *c->h_nf = 0;
-    LO_HIP(c, hipMemset(c->d_st, 0, sizeof(DevState)));
+    LO_HIP(c, hipMemset(cur(c).d_st, 0, sizeof(DevState)));
     // empty table (capacity 2) so a scan before any map upload finds nothing
     c->log2cap = 1;
     LO_HIP(c, c->d_tab.reserve(2));
@@ -210,22 +202,7 @@ lo_ctx* lo_create(const lo_config* cfg, int device, int* err) {
     c->cfg = *cfg;
     c->device = device;
     if (const char* pe = std::getenv("LO_PRESOLVE")) c->presolve = std::atoi(pe) != 0;   // A/B runs
-    // rocprofv3 counter collection serialises dispatches across queues, which the pipeline's device-side waits cannot
-    // survive (k_wait_final): the pipeline starts off under it unless LO_PIPE says otherwise
-    if (const char* cc = std::getenv("ROCPROF_COUNTER_COLLECTION")) {
-        if (*cc && std::strcmp(cc, "0") != 0 && std::strcmp(cc, "False") != 0 && std::strcmp(cc, "false") != 0) c->pipe = false;
-    }
-    if (const char* pp = std::getenv("LO_PIPE")) c->pipe = std::atoi(pp) != 0;
-    // (0: split 0, every GN iteration of a scan on its lane's stream)
-    if (const char* pm = std::getenv("LO_PIPE_MAIN")) { c->pipe_main = std::max(0, std::atoi(pm)); c->pipe_main_auto = false; }
-    if (const char* po = std::getenv("LO_OVERLAP")) c->overlap = std::atoi(po) != 0;
-    if (const char* pd = std::getenv("LO_OVERLAP_DEPTH")) {
-        c->depth = std::min(std::max(std::atoi(pd), 1), kMaxLanes);
-        c->depth_auto = false;
-    }
-    c->depth_used = c->depth;
-    if (const char* pw = std::getenv("LO_PIPE_WAIT_MS")) c->pipe_bound = 100000ull * std::max(1, std::atoi(pw));
-    if (const char* pf = std::getenv("LO_PIPE_FAIL_AT")) c->pipe_fail_at = static_cast<uint32_t>(std::max(0, std::atoi(pf)));
+    c->q.from_env();
     if (const char* pg = std::getenv("LO_PKO_GROUPS")) c->pko_groups = std::max(0, std::atoi(pg));
     if (const char* ps = std::getenv("LO_PKO_SOLO")) c->pko_solo = std::atoi(ps) != 0;
     if (const char* ex = std::getenv("LO_EXACT")) c->exact = std::atoi(ex) != 0;   // A/B runs: LO_EXACT=0 = fast mode
@@ -252,7 +229,7 @@ void lo_destroy(lo_ctx* c) {
     }
     (void)hipSetDevice(c->device);
     (void)sync_all(c);
-    for (hipStream_t s : c->s_tail)
+    for (hipStream_t s : c->q.s_tail)
         if (s) (void)hipStreamDestroy(s);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -290,17 +267,21 @@ int lo_update_config(lo_ctx* c, const lo_config* cfg) {
     }
     c->cfg = *cfg;
     ++c->cfg_gen;                                        // batches re-upload this context's parameters
-    if (na_changed || (cfg->use_adaptive_m_estimator && !c->d_acc_part)) {
-        // the candidate buffers are sized by the alpha grid: re-made on the next optimize (the other lanes whole)
-        c->d_acc_part.reset();
-        c->d_cand_rec.reset();
-        c->d_cand_cnt.reset();
+    if (na_changed || (cfg->use_adaptive_m_estimator && !cur(c).d_acc_part)) {
+        // the candidate buffers are sized by the alpha grid: the current lane's are re-made on the next optimize, every
+        // other lane whole on its next use
         for (int l = 0; l < kMaxLanes; ++l) {
-            if (l == c->lane) continue;
-            c->lanes[l] = lo_ctx::ScanLane{};
-            c->lane_ready[l] = false;
+            ScanLane& L = c->q.lanes[l];
+            if (l == c->q.lane) {
+                L.d_acc_part.reset();
+                L.d_cand_rec.reset();
+                L.d_cand_cnt.reset();
+            } else {
+                L = ScanLane{};
+                c->q.lane_ready[l] = false;
+            }
         }
-        c->prev_lane = -1;
+        c->q.prev_lane = -1;
     }
     return LO_OK;
 }
@@ -321,59 +302,6 @@ int lo_set_pko_groups(lo_ctx* c, int groups) {
     return LO_OK;
 }
 
-int lo_pipeline_status(lo_ctx* c, int out[4]) {
-    if (!c || !out) return LO_ERR_ARG;
-    out[0] = c->pipe ? 1 : 0;
-    out[1] = c->pipe_main;
-    out[2] = static_cast<int>(c->pipe_timeouts);
-    out[3] = static_cast<int>(c->pipe_reruns);
-    return LO_OK;
-}
-
-int lo_set_pipeline(lo_ctx* c, int enable, int main_iterations) {
-    if (!c || main_iterations < 0) return LO_ERR_ARG;
-    const int rc = flush_hold(c);
-    if (rc != LO_OK) return rc;
-    c->pipe = enable != 0;
-    if (main_iterations > 0) { c->pipe_main = main_iterations; c->pipe_main_auto = false; }
-    return LO_OK;
-}
-
-int lo_set_scan_overlap(lo_ctx* c, int enable) {
-    if (!c) return LO_ERR_ARG;
-    const int rc = flush_hold(c);
-    if (rc != LO_OK) return rc;
-    c->overlap = enable != 0;
-    return LO_OK;
-}
-
-int lo_set_scan_depth(lo_ctx* c, int depth) {
-    if (!c || depth < 1 || depth > 2) return LO_ERR_ARG;
-    const int rc = flush_hold(c);
-    if (rc != LO_OK) return rc;
-    c->depth = depth;
-    c->depth_auto = false;
-    return LO_OK;
-}
-
-// The scan ring: up to kMaxLanes queued scans in flight, scan k of a queue on lane k % lanes.  1 and 2 are
-// lo_set_scan_depth's; from 3 on a queue's scans take split 0 unless a split was chosen (enqueue_optimize).
-int lo_set_scan_lanes(lo_ctx* c, int lanes) {
-    if (!c || lanes < 1 || lanes > kMaxLanes) return LO_ERR_ARG;
-    const int rc = flush_hold(c);
-    if (rc != LO_OK) return rc;
-    c->depth = lanes;
-    c->depth_auto = false;
-    return LO_OK;
-}
-
-int lo_scan_overlap_status(lo_ctx* c, long long out[2]) {
-    if (!c || !out) return LO_ERR_ARG;
-    out[0] = c->overlap ? 1 : 0;
-    out[1] = static_cast<long long>(c->overlapped);
-    return LO_OK;
-}
-
 int lo_set_stream(lo_ctx* c, void* stream) {
     if (!c) return LO_ERR_ARG;
     LO_HIP(c, hipSetDevice(c->device));
@@ -388,7 +316,7 @@ int lo_icp_export_pose(lo_ctx* c, float* d_out16) {
     if (!c || !d_out16) return LO_ERR_ARG;
     const int rc = flush_hold(c);
     if (rc != LO_OK) return rc;
-    hipLaunchKernelGGL(k_export_pose, dim3(1), dim3(64), 0, c->stream, c->d_st, d_out16);
+    hipLaunchKernelGGL(k_export_pose, dim3(1), dim3(64), 0, c->stream, cur(c).d_st, d_out16);
     LO_HIP(c, hipGetLastError());
     return LO_OK;
 }

@@ -1,6 +1,6 @@
 // lo_ctx_def.h — the ICP context itself and the helpers its translation units share (lo_ctx, lo_surfel, lo_grid,
-// lo_optimize, lo_hooks, lo_batch .hip).  Nothing else includes this: lo_devmap, lo_iris, lo_gmap and lo_voxelmap reach
-// a context through lo_ctx_internal.h.
+// lo_optimize, lo_scanq, lo_hooks, lo_batch .hip).  Nothing else includes this: lo_devmap, lo_iris, lo_gmap and
+// lo_voxelmap reach a context through lo_ctx_internal.h.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -23,6 +23,7 @@
 #include "lo_kernels_decl.h"
 #include "lo_math.h"
 #include "lo_pko_tables.h"
+#include "lo_scanq.h"
 #include "lo_seqsum.h"
 #include "lo_vfilter.h"
 
@@ -65,17 +66,8 @@ struct lo_ctx {
     std::string err;
     // scan buffers
     DevBuf<float> d_pts;
-    DevBuf<int32_t> d_slot;
-    DevBuf<double> d_res_pko;       // per-point residual of the accepted correspondences (the PKO sample reads it)
-    DevBuf<uint64_t> d_wmask;
-    DevBuf<int32_t> d_blk_cnt;
-    DevBuf<double> d_blk_sum;
-    DevBuf<double> d_blk_m2;
-    DevBuf<double> d_blk_part;
-    DevBuf<double> d_acc_part;      // speculative normal equations (allocated on the first PKO optimize)
-    DevBuf<float> d_cand_rec;       //   and each candidate's solved GN step [NA + 1][kCandWords]
-    DevBuf<unsigned> d_cand_cnt;    //   per-candidate workgroup arrivals (zero between launches)
-    bool presolve = true;           //   candidates solve inside the PKO launch (LO_PRESOLVE=0: k_solve_* instead)
+    ScanQueue q;                    // the scan queue, and the lanes of per-scan state (lo_scanq.h; cur(c) is the current)
+    bool presolve = true;           // candidates solve inside the PKO launch (LO_PRESOLVE=0: k_solve_* instead)
     bool exact = true;              // lo_set_exact: the reference's own arithmetic order (lo_exact.hip) -- the default;
                                     //   lo_set_exact(ctx, 0) opts into the fast mode (fp64 tree sums, not parity-safe)
     uint64_t cfg_gen = 0;           // bumped by lo_update_config and by (re)allocations of the PKO / candidate buffers: a
@@ -93,10 +85,8 @@ struct lo_ctx {
     DevBuf<double> d_ex_res;        //   scans beyond kExactMaxPoints: residuals, sorted residuals, hipCUB scratch
     DevBuf<double> d_ex_sorted;
     DevBuf<void> d_ex_sort_tmp;
-    DevBuf<double> d_js;
     DevBuf<double> d_res;           // parity entry points (per-point residual / direct residual input)
     DevBuf<uint8_t> d_u8;
-    DevBuf<DevState> d_st;
     PinnedBuf<DevState> h_st;
     PinnedBuf<int> h_nf;            // the device-filtered scan's count, read back with the result
     bool nf_valid = false;          //   h_nf holds the last device-filtered scan's count (lo_icp_result)
@@ -163,83 +153,9 @@ struct lo_ctx {
     float T_init[12];
     size_t last_n = 0;
     bool pending = false;
-    // scan pipeline (lo_set_pipeline; on by default): GN iterations >= pipe_main of a small PKO scan go to a tail
-    // stream, and the context stream is held (k_wait_final) only until the scan's result is final -- a converged
-    // scan's early-exit launches drain beside the next scan instead of in front of it.  The tail starts when the main
-    // part is done (k_wait_seq polls the word the main part's last pick sets); no HIP events on the hot path (every
-    // marker packet costs ~5-7 us of device time between two kernels).
-    bool pipe = true;
-    int pipe_main = 1;              // (1: the tail then carries ~1.4 working iterations per scan, and the whole head of
-                                    //   the next scan hides under it)
-    bool pipe_main_auto = true;     // no split chosen (lo_set_pipeline / LO_PIPE_MAIN): only a scan whose own head overlapped
-                                    //   takes pipe_main, every other scan keeps the split 2 it always had -- 1 costs it ~1 %
     int pko_groups = 0;             // EM workgroups per PKO launch (lo_set_pko_groups / LO_PKO_GROUPS; 0 = one per alpha)
     bool pko_solo = false;          // LO_PKO_SOLO=1 (A/B): the speculative PKO launch asks for enough LDS that one
                                     //   workgroup holds a CU alone (no other launch's waves on its SIMDs)
-    static constexpr int kMaxLanes = 4;             // sets of per-scan state, and queued scans in flight at most (scan ring)
-    hipStream_t s_tail[kMaxLanes] = {};   // one tail stream per lane (scan overlap, below), made when a scan first runs
-                                    //   there: a scan's tail does not queue behind the early-exit launches of another lane's
-    uint32_t pipe_seq = 0;          // pipelined scans so far (LO_PIPE_FAIL_AT counts in it)
-    uint32_t lane_seq[kMaxLanes] = {};   // each lane's own sequence number: what its fence words count in (never 0)
-    DevBuf<uint32_t> d_fin;         // kFinWords per lane, kMaxLanes groups (KParams::fin names the lane's group): [0] the
-                                    // lane's last scan whose result is final (publish_final), [1] main part done, [2]
-                                    // signal_main's block count, [3] broken (a wait timed out; sticky, and set in every
-                                    // group: pipe_fail)
-    MappedBuf<uint32_t> h_broken;   // device-mapped: the seq of the scan whose wait timed out (0: none)
-    uint32_t* d_hbroken = nullptr;  //   its device alias (not owned)
-    unsigned long long pipe_bound = 200000000ull;   // wait bound in 100 MHz ticks (2 s; LO_PIPE_WAIT_MS)
-    uint32_t pipe_fail_at = 0;      // test hook (LO_PIPE_FAIL_AT=k): the k-th pipelined scan's tail wait gives up at once
-    unsigned pipe_timeouts = 0;     // times a wait timed out and the pipeline was switched off (lo_pipeline_status)
-    unsigned pipe_reruns = 0;       // synchronous scans re-run on one stream after such a timeout
-    // scan overlap (lo_set_scan_overlap; on by default, LO_OVERLAP=0): a pipelined scan does not end with its
-    // k_wait_final -- the hold is kept pending (hold_seq, hold_st) and enqueued by the next pipelined scan after that
-    // scan's own head (first correspondence launch + exact scale), which therefore runs beside this scan's tail.  The
-    // head writes the per-scan state the tail still reads, so the context owns two sets of it ("lanes"): the members
-    // above are the lane of the last enqueued scan, `alt` is the other one (allocated the first time a scan is enqueued
-    // while another is in flight), and lane_switch swaps them.  Every other entry point that touches the context stream
-    // or a queued scan's inputs enqueues the pending hold first (flush_hold), after which the context is as it was
-    // before this existed.  The map and the PKO tables are shared; each lane has its own fence words and tail stream.
-    // Scan ring (lo_set_scan_lanes): up to kMaxLanes such sets.  `lanes[i]` holds lane i's set while another lane is the
-    // current one (the current lane's entry is empty: its set is the members above); a set is allocated the first time
-    // a scan runs on its lane, so a context that never queues scans pays for none (~1.5 MB each at the default max_points).
-    struct ScanLane {
-        DevBuf<int32_t> d_slot;
-        DevBuf<double> d_res_pko;
-        DevBuf<uint64_t> d_wmask;
-        DevBuf<int32_t> d_blk_cnt;
-        DevBuf<double> d_blk_sum, d_blk_m2, d_blk_part, d_acc_part;
-        DevBuf<float> d_cand_rec;
-        DevBuf<unsigned> d_cand_cnt;
-        DevBuf<double> d_js;
-        DevBuf<DevState> d_st;
-    };
-    ScanLane lanes[kMaxLanes];
-    bool lane_ready[kMaxLanes] = {true, false, false, false};   // lane i has a full set (in lanes[i], or the members when
-                                    //   it is the current one), its candidate buffers sized for the current alpha grid
-    int lane = 0;                   // which set the members above are (scan k of a queue: k % max(depth, 2))
-    int prev_lane = -1;             // the lane the last switch left: the scan enqueued before the last one ran there
-                                    //   (lo_debug_other_lane_record; -1: no scan has overlapped yet)
-    bool overlap = true;
-    // `depth` >= 2 scans in flight (lo_set_scan_depth / lo_set_scan_lanes / LO_OVERLAP_DEPTH): the hold of scan k - 1 is
-    // no longer enqueued by scan k, only the hold of scan k - depth -- the scan that last used scan k's lane -- and in
-    // front of scan k's head.  So up to `depth` holds are pending, and scan k's GN iterations run beside scan k - 1's tail.
-    static constexpr int kDefaultDepth = 4;         // queued scans in flight unless chosen: 4 with split 0 measured +27 % over
-                                                    //   2, and 3 only +2 % (DESIGN.md "Scan ring")
-    struct Hold {
-        uint32_t seq;               // the scan's number on its lane
-        int lane;
-        DevState* st;               // its lane's DevState (a timed-out wait marks it LO_ERR_PIPELINE)
-    };
-    Hold holds[kMaxLanes];          // the scans whose k_wait_final is still to be enqueued, oldest first
-    int n_hold = 0;
-    int depth = kDefaultDepth;
-    bool depth_auto = true;         // no depth chosen: one scan in flight while other contexts queue scans too (scan_depth)
-    int depth_used = kDefaultDepth; // the depth the pending holds were placed for
-    // every pipelined scan's 16-float record (lo_icp_queue_records): the thread that publishes a scan final writes it
-    DevBuf<float> d_ring;           // kRingRecords x 16 floats
-    unsigned long long ring_pos = 0;   // pipelined scans given a slot so far (slot = ring_pos % kRingRecords)
-    unsigned ring_n = 0;            // of which the last ring_n were queued with no other scan in between (<= kRingRecords)
-    unsigned long long overlapped = 0;   // scans whose head was enqueued in front of the previous scan's hold
     const float* last_pts = nullptr;   // the scan in flight (a re-run after a pipeline timeout)
     const int* last_ndev = nullptr;
     bool sync_call = false;         // the optimize in flight is a synchronous call: HIP events time it (gpu_ms)
@@ -248,11 +164,6 @@ struct lo_ctx {
 
 namespace lo {
 constexpr int kStageEvents = 1024;
-constexpr int kFinWords = 4;                          // fence words per lane (lo_ctx::d_fin; pipe_fail relies on the 4)
-constexpr int kMaxLanes = lo_ctx::kMaxLanes;          // (pipe_fail writes every group of the block)
-static_assert(kMaxLanes == kFinLanes && kFinWords == 4, "pipe_fail masks a fence-word address to the block of all lanes");
-constexpr int kRingRecords = 64;                      // lo_icp_queue_records: records kept per context
-constexpr int kRecWords = 16;                         //   floats per record (lo_icp_export_pose's layout)
 constexpr int kExactMaxPoints = 16384;                // reference-exact mode: one-workgroup sort in LDS up to here
 
 // lo_ctx.hip
@@ -274,8 +185,18 @@ bool spec_ok(const KParams& P);
 void launch_pko_spec(lo_ctx* c, const KParams& P, int it, hipStream_t s = nullptr);
 void launch_brute(lo_ctx* c, const KParams& P);
 void launch_correspond(lo_ctx* c, const KParams& P, int with_stats, bool kd);
+void launch_correspond_first(lo_ctx* c, const KParams& P0, bool kd, int with_stats = 1);
+void launch_exact_scale_any(lo_ctx* c, const KParams& P, int n2, hipStream_t s);
 int enqueue_optimize(lo_ctx* c, const float* d_pts, size_t n, const float T_init[12], const int* n_dev = nullptr);
+// lo_scanq.hip
+inline ScanLane& cur(lo_ctx* c) { return c->q.lanes[c->q.lane]; }   // the lane of the last enqueued scan
+int lane_alloc_base(lo_ctx* c, ScanLane& L);    // everything but the candidate buffers, sized by max_points
+int lane_alloc_cand(lo_ctx* c, ScanLane& L);    // the candidate buffers, sized by the alpha grid (d_acc_part last)
 int flush_hold(lo_ctx* c);     // the pending holds of the last pipelined scans, enqueued on the context stream now
+int pipe_recover(lo_ctx* c);
+ScanPlanIn scan_snapshot(const lo_ctx* c, bool cand, bool timed, bool dev_count);
+int apply_plan(lo_ctx* c, const ScanPlan& plan);
+int emit_pipelined(lo_ctx* c, const ScanPlan& plan, KParams& P, KParams& P0, int n2, unsigned ring_run);
 
 // ---- per-scan helpers on the launch path of every optimize, single and batched: inline, as when one file held them
 // PKO workgroups: one alpha of the JS grid per workgroup (each fits the GMM redundantly), capped at kPkoMaxWGs
@@ -289,12 +210,11 @@ inline int pko_grid(const lo_ctx* c) {
 constexpr size_t kPkoSoloBytes = 64 * 1024;   // + the ~22-27 KB static part: more than half of a CU's 160 KB
 // the speculative normal equations and candidate records (first PKO optimize, and after lo_update_config dropped them)
 inline int ensure_acc_part(lo_ctx* c) {
-    if (c->d_acc_part || !c->cfg.use_adaptive_m_estimator) return LO_OK;
-    const size_t cand = static_cast<size_t>(c->cfg.num_alpha_segments) + 1;
-    LO_HIP(c, c->d_cand_rec.reserve(cand * kCandWords));
-    LO_HIP(c, c->d_cand_cnt.reserve(cand));
-    LO_HIP(c, hipMemset(c->d_cand_cnt, 0, cand * sizeof(unsigned)));
-    LO_HIP(c, c->d_acc_part.reserve(cand * kFuseMaxBlocks * kNE));   // last: the guard above reads it as "all three"
+    ScanLane& L = cur(c);
+    if (L.d_acc_part || !c->cfg.use_adaptive_m_estimator) return LO_OK;    // (set last: "all three")
+    const int rc = lane_alloc_cand(c, L);
+    if (rc != LO_OK) return rc;
+    LO_HIP(c, hipMemset(L.d_cand_cnt, 0, L.d_cand_cnt.capacity() * sizeof(unsigned)));
     ++c->cfg_gen;
     // the exact candidates' staging sits in the PKO launch's dynamic LDS (beyond the 64 KB default with the static part)
     LO_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pko_tx), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -363,21 +283,22 @@ inline KParams make_params(lo_ctx* c, const float* d_pts, int n) {
     P.ev_off = c->d_tabs_i + c->off_ev_off;
     P.ev_steps = c->d_tabs_i + c->off_ev_steps;
     P.km_draws = c->d_tabs_i + c->off_km;
-    P.slot = c->d_slot;
-    P.wmask = c->d_wmask;
-    P.blk_cnt = c->d_blk_cnt;
-    P.blk_sum = c->d_blk_sum;
-    P.blk_m2 = c->d_blk_m2;
-    P.blk_part = c->d_blk_part;
-    P.acc_part = c->d_acc_part;
-    P.cand_rec = c->presolve ? c->d_cand_rec : nullptr;   // candidates pre-solve (k_pick*, KDTree: k_pick_knn)
-    P.cand_cnt = c->d_cand_cnt;
-    P.js = c->d_js;
+    const ScanLane& L = cur(c);
+    P.slot = L.d_slot;
+    P.wmask = L.d_wmask;
+    P.blk_cnt = L.d_blk_cnt;
+    P.blk_sum = L.d_blk_sum;
+    P.blk_m2 = L.d_blk_m2;
+    P.blk_part = L.d_blk_part;
+    P.acc_part = L.d_acc_part;
+    P.cand_rec = c->presolve ? L.d_cand_rec.get() : nullptr;   // candidates pre-solve (k_pick*, KDTree: k_pick_knn)
+    P.cand_cnt = L.d_cand_cnt;
+    P.js = L.d_js;
     P.res_dbg = nullptr;
-    P.res_out = c->d_res_pko;
+    P.res_out = L.d_res_pko;
     P.direct_res = nullptr;
-    P.st = c->d_st;
-    P.em_stat = c->stage_timing ? reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(c->d_st.get()) +
+    P.st = L.d_st;
+    P.em_stat = c->stage_timing ? reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(L.d_st.get()) +
                                                                         offsetof(DevState, em_stat))
                                 : nullptr;                  // the lead PKO workgroup's EM clock (stage timing)
     if (c->kd) set_kd_params(c, P, c->grid);             // KDTree path: downstream kernels read per-point planes

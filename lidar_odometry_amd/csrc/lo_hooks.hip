@@ -60,7 +60,7 @@ static int ensure_res(lo_ctx* c, size_t n) {
 static int reset_state(lo_ctx* c, const float T[12], double scale, double alpha) {
     Pose12 T0;
     std::memcpy(T0.v, T, sizeof(float) * 12);
-    hipLaunchKernelGGL(k_init, dim3(1), dim3(64), 0, c->stream, c->d_st, T0, scale, alpha);
+    hipLaunchKernelGGL(k_init, dim3(1), dim3(64), 0, c->stream, cur(c).d_st, T0, scale, alpha);
     LO_HIP(c, hipGetLastError());
     return LO_OK;
 }
@@ -81,7 +81,7 @@ int lo_find_correspondences(lo_ctx* c, const float* pts, size_t n, const float T
     launch_correspond(c, P, 1, c->kd);
     LO_HIP(c, hipGetLastError());
     std::vector<int32_t> slots(n);
-    LO_HIP(c, hipMemcpyAsync(slots.data(), c->d_slot, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    LO_HIP(c, hipMemcpyAsync(slots.data(), cur(c).d_slot, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     LO_HIP(c, hipMemcpyAsync(residual, c->d_res, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     LO_HIP(c, hipStreamSynchronize(c->stream));
     int cnt = 0;
@@ -146,7 +146,7 @@ double lo_pko_scale_factor(lo_ctx* c, const double* residuals, size_t n, double*
     launch_pko(c, P, 0);
     hipLaunchKernelGGL(k_pko_finish, dim3(1), dim3(64), 0, c->stream, P);
     if (hipGetLastError() != hipSuccess) return NAN;
-    if (hipMemcpyAsync(c->h_st, c->d_st, sizeof(DevState), hipMemcpyDeviceToHost, c->stream) != hipSuccess) return NAN;
+    if (hipMemcpyAsync(c->h_st, cur(c).d_st, sizeof(DevState), hipMemcpyDeviceToHost, c->stream) != hipSuccess) return NAN;
     if (hipStreamSynchronize(c->stream) != hipSuccess) return NAN;
     if (gmm_out) for (int j = 0; j < 3 * c->cfg.gmm_components; ++j) gmm_out[j] = c->h_st->gmm_out[j];
     return c->h_st->alpha;
@@ -173,8 +173,8 @@ int lo_build_normal_equations(lo_ctx* c, const float* pts, size_t n, const float
     }
     LO_HIP(c, hipGetLastError());
     std::vector<int32_t> cnt(P.nb);
-    LO_HIP(c, hipMemcpyAsync(cnt.data(), c->d_blk_cnt, P.nb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    LO_HIP(c, hipMemcpyAsync(c->h_st, c->d_st, sizeof(DevState), hipMemcpyDeviceToHost, c->stream));
+    LO_HIP(c, hipMemcpyAsync(cnt.data(), cur(c).d_blk_cnt, P.nb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    LO_HIP(c, hipMemcpyAsync(c->h_st, cur(c).d_st, sizeof(DevState), hipMemcpyDeviceToHost, c->stream));
     LO_HIP(c, hipStreamSynchronize(c->stream));
     for (int q = 0; q < 36; ++q) H[q] = c->h_st->H_out[q];
     for (int j = 0; j < 6; ++j) g[j] = c->h_st->g_out[j];
@@ -269,10 +269,10 @@ int lo_pko_em_stats(lo_ctx* c, unsigned long long out[3], int reset) {
     if (!c || !out) return LO_ERR_ARG;
     LO_HIP(c, hipSetDevice(c->device));
     LO_HIP(c, sync_all(c));
-    LO_HIP(c, hipMemcpy(out, reinterpret_cast<const char*>(c->d_st.get()) + offsetof(DevState, em_stat),
+    LO_HIP(c, hipMemcpy(out, reinterpret_cast<const char*>(cur(c).d_st.get()) + offsetof(DevState, em_stat),
                         3 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     if (reset)
-        LO_HIP(c, hipMemset(reinterpret_cast<char*>(c->d_st.get()) + offsetof(DevState, em_stat), 0, 3 * sizeof(unsigned long long)));
+        LO_HIP(c, hipMemset(reinterpret_cast<char*>(cur(c).d_st.get()) + offsetof(DevState, em_stat), 0, 3 * sizeof(unsigned long long)));
     return LO_OK;
 }
 
@@ -452,10 +452,10 @@ int lo_debug_cand_records(lo_ctx* c, float* out, size_t cap_words) {
     if (!c || !out) return LO_ERR_ARG;
     { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
     const size_t cand = static_cast<size_t>(c->cfg.num_alpha_segments) + 1, words = cand * kCandWords;
-    if (!c->d_acc_part || c->d_cand_rec.capacity() < words) { c->err = "lo_debug_cand_records: no records yet"; return LO_ERR_STATE; }
+    if (!cur(c).d_acc_part || cur(c).d_cand_rec.capacity() < words) { c->err = "lo_debug_cand_records: no records yet"; return LO_ERR_STATE; }
     if (cap_words < words) { c->err = "lo_debug_cand_records: output too small"; return LO_ERR_CAPACITY; }
     LO_HIP(c, sync_all(c));
-    LO_HIP(c, hipMemcpy(out, c->d_cand_rec, words * sizeof(float), hipMemcpyDeviceToHost));
+    LO_HIP(c, hipMemcpy(out, cur(c).d_cand_rec, words * sizeof(float), hipMemcpyDeviceToHost));
     return static_cast<int>(cand);
 }
 
@@ -465,12 +465,12 @@ int lo_debug_other_lane_record(lo_ctx* c, float out16[16]) {
     if (!c || !out16) return LO_ERR_ARG;
     LO_HIP(c, hipSetDevice(c->device));
     LO_HIP(c, sync_all(c));
-    if (c->prev_lane < 0 || !c->lanes[c->prev_lane].d_st) {
+    if (c->q.prev_lane < 0 || !c->q.lanes[c->q.prev_lane].d_st) {
         c->err = "lo_debug_other_lane_record: no scan has overlapped yet";
         return LO_ERR_STATE;
     }
     std::vector<char> h(offsetof(DevState, logs));
-    LO_HIP(c, hipMemcpy(h.data(), c->lanes[c->prev_lane].d_st.get(), h.size(), hipMemcpyDeviceToHost));
+    LO_HIP(c, hipMemcpy(h.data(), c->q.lanes[c->q.prev_lane].d_st.get(), h.size(), hipMemcpyDeviceToHost));
     const DevState* st = reinterpret_cast<const DevState*>(h.data());   // (header fields only)
     for (int k = 0; k < 12; ++k) out16[k] = st->pose[k];
     out16[12] = static_cast<float>(st->status);
@@ -483,7 +483,7 @@ int lo_debug_other_lane_record(lo_ctx* c, float out16[16]) {
 int lo_debug_counters(lo_ctx* c, unsigned long long out[16]) {
     if (!c || !out) return LO_ERR_ARG;
     LO_HIP(c, sync_all(c));
-    const DevState* st = c->d_st;
+    const DevState* st = cur(c).d_st;
     LO_HIP(c, hipMemcpy(out, reinterpret_cast<const char*>(st) + offsetof(DevState, dbg), 16 * sizeof(unsigned long long),
                         hipMemcpyDeviceToHost));
     return LO_OK;
@@ -519,7 +519,7 @@ int lo_debug_grid(lo_ctx* c, float* h, int org[3], int dim[3], int* m, uint32_t*
 int lo_debug_counters_ex(lo_ctx* c, unsigned long long* out, int n) {
     if (!c || !out || n < 1 || n > 24) return LO_ERR_ARG;
     LO_HIP(c, sync_all(c));
-    LO_HIP(c, hipMemcpy(out, reinterpret_cast<const char*>(c->d_st.get()) + offsetof(DevState, dbg),
+    LO_HIP(c, hipMemcpy(out, reinterpret_cast<const char*>(cur(c).d_st.get()) + offsetof(DevState, dbg),
                         static_cast<size_t>(n) * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return LO_OK;
 }

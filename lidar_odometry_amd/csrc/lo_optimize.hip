@@ -5,8 +5,6 @@
 // between; the kernels read DevState::done and fall through once the scan has converged or failed.
 #include <hipcub/hipcub.hpp>
 
-#include <atomic>
-
 #include "lo_ctx_def.h"
 
 namespace lo {
@@ -54,78 +52,6 @@ static void launch_gn_tail(lo_ctx* c, const KParams& P, int it) {
     }
 }
 
-// Scan pipeline (first pipelined scan): the lanes' tail streams, their fence words, the record ring, the host flag.
-static int pipe_alloc(lo_ctx* c) {
-    if (c->d_hbroken) return LO_OK;                 // set last
-    // (the first lane's tail stream; another lane's is made when a scan first runs there with two or more in flight)
-    if (!c->s_tail[0]) LO_HIP(c, hipStreamCreateWithFlags(&c->s_tail[0], hipStreamNonBlocking));
-    // (pipe_fail finds every group from any one: kMaxLanes x 16 bytes, aligned to that -- hipMalloc aligns to 256)
-    LO_HIP(c, c->d_fin.reserve(kMaxLanes * kFinWords));
-    LO_HIP(c, hipMemset(c->d_fin, 0, kMaxLanes * kFinWords * sizeof(uint32_t)));
-    LO_HIP(c, c->d_ring.reserve(static_cast<size_t>(kRingRecords) * kRecWords));
-    LO_HIP(c, hipMemset(c->d_ring, 0, static_cast<size_t>(kRingRecords) * kRecWords * sizeof(float)));
-    LO_HIP(c, c->h_broken.reserve(1));
-    *c->h_broken = 0;
-    LO_HIP(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_hbroken), c->h_broken, 0));
-    LO_HIP(c, hipDeviceSynchronize());              // zeroed before either stream's first poll
-    return LO_OK;
-}
-
-// A pipeline wait timed out (the dispatcher ran the streams out of submission order): drain the context stream and every
-// lane stream, switch the pipeline off for this context, clear the flag words.  Scans enqueued before this point report
-// LO_ERR_PIPELINE (their tails left without touching anything); a synchronous call re-runs its scan on one stream
-// (lo_icp_result).
-static int pipe_recover(lo_ctx* c) {
-    LO_HIP(c, sync_all(c));                         // (enqueues the pending holds of every lane first: they give up at once)
-    c->pipe = false;
-    ++c->pipe_timeouts;
-    c->ring_n = 0;                                  // (the records of the scans that gave up were never written)
-    c->err = "scan pipeline: a device-side wait timed out (the streams were not run concurrently, e.g. rocprofv3 "
-             "counter collection); pipeline switched off for this context";
-    LO_HIP(c, hipMemset(c->d_fin, 0, kMaxLanes * kFinWords * sizeof(uint32_t)));
-    for (uint32_t& s : c->lane_seq) s = 0;          // (with the words they count in)
-    LO_HIP(c, hipStreamSynchronize(nullptr));
-    __atomic_store_n(c->h_broken.get(), 0u, __ATOMIC_RELEASE);
-    return LO_OK;
-}
-static bool pipe_flagged(const lo_ctx* c) { return c->h_broken && __atomic_load_n(c->h_broken.get(), __ATOMIC_ACQUIRE) != 0u; }
-
-// Contexts of this process with a hold pending, i.e. with queued scans in flight right now.
-static std::atomic<int> g_holding{0};
-// Scan overlap: the one place a pending hold leaves the host -- the oldest one, on the context stream.  The wait is
-// k_wait_final's as before: bounded by pipe_bound, it gives up at once when the pipeline is broken, and a timeout marks
-// the held scan's own DevState (its lane's) LO_ERR_PIPELINE.
-static int pop_hold(lo_ctx* c) {
-    const lo_ctx::Hold h = c->holds[0];
-    for (int i = 1; i < c->n_hold; ++i) c->holds[i - 1] = c->holds[i];
-    if (--c->n_hold == 0) g_holding.fetch_sub(1, std::memory_order_relaxed);
-    LO_HIP(c, hipSetDevice(c->device));
-    hipLaunchKernelGGL(k_wait_final, dim3(1), dim3(kWave), 0, c->stream, c->d_fin + kFinWords * h.lane, h.seq, h.st,
-                       c->d_hbroken, c->pipe_bound);
-    LO_HIP(c, hipGetLastError());
-    return LO_OK;
-}
-// All pending holds, oldest first.  Called at the top of every entry point that enqueues on the context stream, reads
-// from it, or changes what a queued scan reads (and by sync_all); enqueue_optimize places the holds of a queue of scans
-// itself (pop_hold).
-int flush_hold(lo_ctx* c) {
-    while (c->n_hold > 0) {
-        const int rc = pop_hold(c);
-        if (rc != LO_OK) return rc;
-    }
-    return LO_OK;
-}
-
-// Scans in flight for the scan being enqueued.  Two pay while the chip is half idle under one context's queue; when
-// other contexts of the process are queueing scans too, their launches already fill it, and a second scan in flight per
-// context only adds waits to the few hardware queues all their streams share (8 contexts: 24 streams on 4 queues ran
-// 31 % slower in aggregate).  So unless lo_set_scan_depth / LO_OVERLAP_DEPTH chose, a context that is not alone in
-// having scans in flight keeps one.
-static int scan_depth(const lo_ctx* c) {
-    if (!c->depth_auto) return c->depth;
-    const int others = g_holding.load(std::memory_order_relaxed) - (c->n_hold > 0 ? 1 : 0);
-    return others > 0 ? 1 : c->depth;
-}
 // A small scan whose PKO launches pre-solve the candidates (k_pick* selects one): the launch sequence of the fast mode,
 // in reference-exact mode with the one-workgroup sort.  enqueue_optimize computes this once, before the lanes are
 // chosen, and every branch below tests it; the KParams it is later built into must agree (checked there).
@@ -135,61 +61,6 @@ static bool cand_scan(const lo_ctx* c, size_t n) {
     return n > 0 && g.use_adaptive_m_estimator && c->presolve && nb <= static_cast<size_t>(kFuseMaxBlocks) &&
            g.max_iterations <= LO_MAX_ITERS && (!c->exact || n <= static_cast<size_t>(kExactMaxPoints));
 }
-// ... that goes down the scan pipeline with the split pipe_main: the only path whose head may overlap the previous
-// scan's tail
-static bool pipelined_scan(const lo_ctx* c, bool cand, int pipe_main) {
-    return cand && !c->kd && c->pipe && c->cfg.max_iterations > pipe_main;
-}
-
-// The context's members <-> a lane's set
-static void lane_swap(lo_ctx* c, lo_ctx::ScanLane& A) {
-    std::swap(A.d_slot, c->d_slot);
-    std::swap(A.d_res_pko, c->d_res_pko);
-    std::swap(A.d_wmask, c->d_wmask);
-    std::swap(A.d_blk_cnt, c->d_blk_cnt);
-    std::swap(A.d_blk_sum, c->d_blk_sum);
-    std::swap(A.d_blk_m2, c->d_blk_m2);
-    std::swap(A.d_blk_part, c->d_blk_part);
-    std::swap(A.d_acc_part, c->d_acc_part);
-    std::swap(A.d_cand_rec, c->d_cand_rec);
-    std::swap(A.d_cand_cnt, c->d_cand_cnt);
-    std::swap(A.d_js, c->d_js);
-    std::swap(A.d_st, c->d_st);
-}
-// Lane `to` becomes the current one: a full set of the per-scan state on its first use (same sizes as ctx_alloc's and
-// ensure_acc_part's), then the current set is parked in its own entry and lane `to`'s taken out of its entry.
-// Depth 1: nothing of the lane swapped in is in flight, its last scan's hold was enqueued before the scan now pending
-// started.  Depth >= 2: that hold may still be pending, and the caller enqueues it before anything touches the lane.
-static int lane_switch(lo_ctx* c, int to) {
-    lo_ctx::ScanLane& A = c->lanes[to];
-    if (!c->lane_ready[to]) {
-        const lo_config& g = c->cfg;
-        const size_t NB = (static_cast<size_t>(g.max_points) + kBlock - 1) / kBlock;
-        const size_t cand = static_cast<size_t>(g.num_alpha_segments) + 1;
-        LO_HIP(c, A.d_slot.reserve(NB * kBlock));
-        LO_HIP(c, A.d_res_pko.reserve(NB * kBlock));
-        LO_HIP(c, A.d_wmask.reserve(NB * kWavesPerBlock));
-        LO_HIP(c, A.d_blk_cnt.reserve(NB));
-        LO_HIP(c, A.d_blk_sum.reserve(NB));
-        LO_HIP(c, A.d_blk_m2.reserve(NB));
-        LO_HIP(c, A.d_blk_part.reserve(NB * kNE));
-        LO_HIP(c, A.d_js.reserve(kMaxAlpha + 1));
-        LO_HIP(c, A.d_st.reserve(1));
-        LO_HIP(c, hipMemsetAsync(A.d_st, 0, sizeof(DevState), c->stream));
-        LO_HIP(c, A.d_cand_rec.reserve(cand * kCandWords));
-        LO_HIP(c, A.d_cand_cnt.reserve(cand));
-        // zeroed on the context stream: this scan's head follows there, and its tail starts only behind its main part
-        LO_HIP(c, hipMemsetAsync(A.d_cand_cnt, 0, cand * sizeof(unsigned), c->stream));
-        LO_HIP(c, A.d_acc_part.reserve(cand * kFuseMaxBlocks * kNE));
-        c->lane_ready[to] = true;
-    }
-    lane_swap(c, c->lanes[c->lane]);                    // (that entry was empty: the members are now)
-    lane_swap(c, A);
-    c->lane = to;
-    ++c->cfg_gen;                                       // a batch's cached device KParams name the other lane's buffers
-    return LO_OK;
-}
-
 
 // ---------------------------------------------------------------- optimize
 // Correspondence stage of one GN iteration: surfel lookup, or (KDTree variant) grid kNN + brute-force
@@ -249,7 +120,7 @@ static void launch_pick_knn(lo_ctx* c, const KParams& P, int it) {
 
 // A scan's first correspondence launch, bracketed by HIP events on the context stream when stage timing is on
 // (the kernel's in-step duration, as opposed to lo_bench_kernel's back-to-back launches).
-static void launch_correspond_first(lo_ctx* c, const KParams& P0, bool kd, int with_stats = 1) {
+void launch_correspond_first(lo_ctx* c, const KParams& P0, bool kd, int with_stats) {
     const bool timed = c->stage_timing && c->st_n < kStageEvents;
     if (timed) (void)hipEventRecord(c->st_ev[2 * c->st_n], c->stream);
     if (timed && !kd && c->d_span) {                     // and its own execution span (k_correspond, P.span)
@@ -319,7 +190,7 @@ static int exact_prepare(lo_ctx* c, KParams& P, size_t n, int* n2) {
     return LO_OK;
 }
 // the iteration-0 scale of reference-exact mode (between the scan's first correspondence launch and its first PKO)
-static void launch_exact_scale_any(lo_ctx* c, const KParams& P, int n2, hipStream_t s) {
+void launch_exact_scale_any(lo_ctx* c, const KParams& P, int n2, hipStream_t s) {
     if (c->ex_merge) {
         launch_exact_scale_c(P, s);                          // counting sort + sums in one workgroup (<= 16384 points)
         return;
@@ -350,77 +221,67 @@ static void launch_exact_iteration(lo_ctx* c, const KParams& P, const KParams& P
     }
 }
 
+// The GN loop on the context stream alone.  fused (small scan with PKO): the solve of iteration it runs fused with the
+// correspondence search of it + 1 (k_solve_correspond; KDTree: k_solve_knn, then k_knn_brute + k_plane), the last
+// solve alone (k_solve_pick).
+static void emit_single(lo_ctx* c, const KParams& P, const KParams& P0, int n2, bool fused) {
+    const int iters = c->cfg.max_iterations;
+    for (int it = 0; it < iters; ++it) {
+        if (!fused) {
+            if (it == 0) launch_correspond_first(c, P0, c->kd);
+            else launch_correspond(c, P, 0, c->kd);
+            launch_gn_tail(c, P, it);
+            continue;
+        }
+        if (it == 0) {
+            launch_correspond_first(c, P0, c->kd);
+            if (c->exact) launch_exact_scale_any(c, P, n2, c->stream);
+        }
+        launch_pko_spec(c, P, it);
+        if (it + 1 < iters && !c->kd) {
+            if (P.cand_rec) hipLaunchKernelGGL(k_pick_correspond, dim3(P.nb), dim3(kBlock), 0, c->stream, P, it);
+            else hipLaunchKernelGGL(k_solve_correspond, dim3(P.nb), dim3(kBlock), 0, c->stream, P, it);
+        } else if (it + 1 < iters) {
+            launch_pick_knn(c, P, it);
+        } else if (P.cand_rec) {
+            hipLaunchKernelGGL(k_pick, dim3(1), dim3(kBlock), 0, c->stream, P, it);
+        } else {
+            hipLaunchKernelGGL(k_solve_pick, dim3(1), dim3(kBlock), 0, c->stream, P, it);
+        }
+    }
+}
+
+// One scan: snapshot of the queue, plan (lo_scan_plan.h), the plan's flush / lane switch / holds, the scan's KParams,
+// then its launches -- down the scan pipeline (emit_pipelined) or on the context stream alone.
 int enqueue_optimize(lo_ctx* c, const float* d_pts, size_t n, const float T_init[12], const int* n_dev) {
     const lo_config& g = c->cfg;
     std::memcpy(c->T_init, T_init, sizeof(float) * 12);
     c->last_n = n;
     c->last_pts = d_pts;
     c->last_ndev = n_dev;
-    const unsigned ring_n0 = c->ring_n;                   // the run of pipelined scans ends here unless this is one
-    c->ring_n = 0;
-    // reset the GN state (pose by kernel argument: no host staging buffer, scans can queue back to back)
-    Pose12 T0;
-    std::memcpy(T0.v, T_init, sizeof(float) * 12);
+    const unsigned ring_run = c->q.ring_n;                // the run of pipelined scans ends here unless this is one
+    c->q.ring_n = 0;
     // HIP events only for synchronous calls (gpu_ms): a marker packet costs ~5-7 us of device time per scan
     const bool timed = c->sync_call;
     c->last_timed = timed;
-    // scan overlap: a hold may be deferred (and a deferred one kept past this scan's head) only between two pipelined
-    // scans that nothing times -- a synchronous call's HIP events and the stage timing bracket the whole scan -- and
-    // whose points are the caller's: a device-filtered scan sits in the context's one point buffer, which the next
-    // raw call's filter overwrites, so that call enqueues the hold first anyway
     const bool cand = cand_scan(c, n);
-    const int depth = scan_depth(c);
-    if (depth != c->depth_used) {                         // the holds pending were placed for the other order: all out first
-        const int rcd = flush_hold(c);
-        if (rcd != LO_OK) return rcd;
-        c->depth_used = depth;
-    }
-    const bool may_defer = c->overlap && !timed && !c->stage_timing && !n_dev && !pipe_flagged(c);
-    // this scan's head overlaps: a hold is pending and the scan is pipelined.  Only then does it take the queue's split
-    // (pipe_main, 1 by default): the caller is queueing scans back to back, and the next head hides under a longer tail.
-    // A scan behind a flushed hold (its caller read the previous result, or made any other call) keeps the split 2 a
-    // scan always had unless one was chosen -- split 1 without overlap costs about 1 %.
-    // Three or more in flight and no split chosen: the queue's split is 0 -- every GN iteration of an overlapping scan
-    // runs on its lane's stream, and the context stream carries only the heads and the holds (DESIGN.md "Scan ring").
-    const int queue_main = (c->pipe_main_auto && depth >= 3) ? 0 : c->pipe_main;
-    const bool overlaps = c->n_hold != 0 && may_defer && pipelined_scan(c, cand, queue_main);
-    const int pipe_main = (c->pipe_main_auto && !overlaps) ? 2 : queue_main;
-    const bool defer = may_defer && pipelined_scan(c, cand, pipe_main);
-    const int lane_before = c->lane;
-    if (c->n_hold != 0) {
-        if (!overlaps) {                                  // any other path: the context as it always was
-            const int rcf = flush_hold(c);
-            if (rcf != LO_OK) return rcf;
-        } else {                                          // this scan's state goes to the next lane of the ring
-            const int rcl = lane_switch(c, (c->lane + 1) % std::max(depth, 2));
-            if (rcl != LO_OK) return rcl;
-            // ... which scan k - depth used.  Two or more in flight: its hold may still be pending (with every older
-            // one), and goes in front of this scan's head, which rewrites the state that scan's tail reads.
-            // (Never more than `depth` in flight either, whatever lanes an earlier depth left the holds on.)
-            int pops = c->n_hold - depth + 1;
-            for (int i = 0; i < c->n_hold; ++i)
-                if (c->holds[i].lane == c->lane) pops = std::max(pops, i + 1);
-            for (int i = 0; depth > 1 && i < pops; ++i) {
-                const int rch = pop_hold(c);
-                if (rch != LO_OK) return rch;
-            }
-        }
-    }
-    if (c->lane != lane_before) c->prev_lane = lane_before;
+    const ScanPlan plan = plan_scan(scan_snapshot(c, cand, timed, n_dev != nullptr));
+    const int rcp = apply_plan(c, plan);
+    if (rcp != LO_OK) return rcp;
     if (timed) LO_HIP(c, hipEventRecord(c->ev0, c->stream));
     if (n == 0) {
-        hipLaunchKernelGGL(k_init, dim3(1), dim3(64), 0, c->stream, c->d_st, T0, 1.0, g.robust_loss_delta);
+        // reset the GN state (pose by kernel argument: no host staging buffer, scans can queue back to back)
+        Pose12 T0;
+        std::memcpy(T0.v, T_init, sizeof(float) * 12);
+        hipLaunchKernelGGL(k_init, dim3(1), dim3(64), 0, c->stream, cur(c).d_st, T0, 1.0, g.robust_loss_delta);
     } else {
         const int rc = ensure_acc_part(c);
         if (rc != LO_OK) return rc;
         KParams P = make_params(c, d_pts, static_cast<int>(n));
         P.n_dev = n_dev;                                  // device-filtered scan: count read on the device
+        std::memcpy(P.T0, T_init, sizeof(float) * 12);    // k_solve_correspond's pose before iteration 0
         KParams P0 = P;                                   // first k_correspond also resets the GN state
         P0.init = 1;
-        std::memcpy(P0.T0, T_init, sizeof(float) * 12);
-        std::memcpy(P.T0, T_init, sizeof(float) * 12);   // k_solve_correspond's pose before iteration 0
-        // small scan with PKO: the solve of iteration it runs fused with the correspondence search of it + 1
-        // (k_solve_correspond; KDTree: k_solve_knn, then k_knn_brute + k_plane), the last solve alone (k_solve_pick)
         const bool fused = spec_ok(P) && g.max_iterations <= LO_MAX_ITERS;
         if (cand != (fused && P.cand_rec != nullptr && (!c->exact || n <= static_cast<size_t>(kExactMaxPoints)))) {
             c->err = "enqueue_optimize: cand_scan disagrees with the scan's parameters";
@@ -432,129 +293,24 @@ int enqueue_optimize(lo_ctx* c, const float* d_pts, size_t n, const float T_init
             if (rc3 != LO_OK) return rc3;
             P0.ex_terms = P.ex_terms;
             P0.scale_given = P.scale_given;
-            if (!cand) {                                  // (n2 > 0 exactly when n <= kExactMaxPoints)
-                // reference-exact GN loop without candidates (lo_exact.hip): correspondences, (iteration 0) sorted-order
-                // scale, PKO, per-point fp32 terms, sequential sums + fp32 LDLT + SVD-projected update
-                for (int it = 0; it < g.max_iterations; ++it) launch_exact_iteration(c, P, P0, it, n2, c->kd);
-                LO_HIP(c, hipGetLastError());
-                if (timed) LO_HIP(c, hipEventRecord(c->ev1, c->stream));
-                c->pending = true;
-                return LO_OK;
-            }
             // small scans with PKO: the same launch sequence as the default mode, with the sorted-order scale after the
             // first correspondence launch and the PKO launch's candidates forming the reference's sequential sums
-            P.exact_cand = P0.exact_cand = 1;
+            if (cand) P.exact_cand = P0.exact_cand = 1;
         }
-        if (pipe_flagged(c)) {                            // an earlier scan's wait timed out: one stream from now on
-            const int rc4 = pipe_recover(c);
-            if (rc4 != LO_OK) return rc4;
-        }
-        if (pipelined_scan(c, cand, pipe_main)) {         // (c->pipe as it is now: a recovery above switched it off)
-            // scan pipeline: iterations < pipe_main on the context stream, the rest on the tail stream behind a
-            // device-side wait for the main part; k_wait_final then holds the context stream until the scan's result
-            // is final
-            const int rc2 = pipe_alloc(c);
-            if (rc2 != LO_OK) return rc2;
-            if (++c->pipe_seq == 0) c->pipe_seq = 1;      // (the test hook's count: LO_PIPE_FAIL_AT is never 0)
-            const bool fail = c->pipe_fail_at != 0 && c->pipe_seq == c->pipe_fail_at;
-            const int lane = c->lane;
-            if (++c->lane_seq[lane] == 0) c->lane_seq[lane] = 1;   // 0 is the fence word's reset value, never a scan's number
-            const uint32_t seq = c->lane_seq[lane];
-            uint32_t* const fin = c->d_fin + kFinWords * lane;
-            // one scan in flight: both lanes' tails on the first tail stream, as before there were two -- tail(k) starts
-            // behind tail(k - 1) anyway, and a third stream per context only crowds the hardware queues of a process
-            // that runs many contexts
-            const int tl = depth > 1 ? lane : 0;
-            if (!c->s_tail[tl]) LO_HIP(c, hipStreamCreateWithFlags(&c->s_tail[tl], hipStreamNonBlocking));
-            const hipStream_t s_tail = c->s_tail[tl];
-            P.fin = P0.fin = fin;
-            P.seq = P0.seq = seq;
-            P.rec = P0.rec = c->d_ring + static_cast<size_t>(c->ring_pos % kRingRecords) * kRecWords;
-            ++c->ring_pos;
-            c->ring_n = std::min<unsigned>(ring_n0 + 1, kRingRecords);
-            KParams Pt = P;                               // tail launches: leave once scan seq is final (the
-            Pt.tail = 1;                                  // DevState may already be the next scan's)
-            KParams Ph = P;                               // the main part's last pick signals the tail (signal_main)
-            Ph.hold = 1;
-            // host submission order of a queue of scans with d = depth >= 2 in flight, scan k on lane k % d:
-            //   context stream:     k_wait_final(k - d) -> head(k) -> main(k)     (the wait was placed above)
-            //   lane stream k % d:  k_wait_seq(k) -> tail(k)
-            // and k_wait_final(k) is placed by scan k + d, or by flush_hold.  main(k) is the iterations below the split:
-            // with split 0 (the queue's split from three in flight on) there is none, the context stream carries
-            // k_wait_final(k - d) -> head(k) -> k_signal_main(k), and every iteration is tail(k).  With one scan in
-            // flight (depth 1) the context stream carries head(k) -> k_wait_final(k - 1) -> main(k) instead.
-            // Every device-side wait depends only on work submitted before it, on any stream: k_wait_final(j) polls
-            // the lane's word that main(j) or tail(j) publishes, both submitted during scan j's own call, which
-            // returned before any call that can place that wait; k_wait_seq(k) polls the lane's word that main(k)'s
-            // last pick sets -- with split 0 the one k_signal_main(k) sets behind head(k) -- submitted just above it,
-            // or the one main(k) publishes when it ends the scan.  Nothing waits for a later submission, so the order
-            // is deadlock-free even if all the streams share one hardware queue (they then simply run in this order),
-            // and every wait is bounded by pipe_bound besides.
-            // head(k) rewrites the lane state of scan k - d: k_wait_final(k - d) precedes it on this stream, so that
-            // scan is final, and what is left of its tail leaves on tail_gone before touching anything.  The lane's
-            // words count the lane's own scans, which are final in order; between the lanes no order is assumed --
-            // scan k may be final before scan k - 1.  main(k) and main(k - 1) follow each other on this stream; with
-            // split 0 tail(k) and tail(k - 1) share nothing but the map and the tables, which neither writes.
-            launch_correspond_first(c, P0, false);
-            if (c->exact) launch_exact_scale_any(c, P, n2, c->stream);
-            // split 0: no pick of a main part to say so -- "head done" is one more launch behind the head (the head's
-            // stores are out when it starts; it releases and sets the lane's word).  The context stream is not the
-            // bound once the iterations have left it.
-            if (pipe_main == 0) hipLaunchKernelGGL(k_signal_main, dim3(1), dim3(kWave), 0, c->stream, fin, seq);
-            if (overlaps) ++c->overlapped;                // its head went in front of the previous scan's hold
-            if (c->n_hold != 0 && depth <= 1) {        // one scan in flight: that hold now, behind this scan's head
-                const int rcf = flush_hold(c);
-                if (rcf != LO_OK) return rcf;
+        if (c->exact && !cand) {                          // (n2 > 0 exactly when n <= kExactMaxPoints)
+            // reference-exact GN loop without candidates (lo_exact.hip): correspondences, (iteration 0) sorted-order
+            // scale, PKO, per-point fp32 terms, sequential sums + fp32 LDLT + SVD-projected update
+            for (int it = 0; it < g.max_iterations; ++it) launch_exact_iteration(c, P, P0, it, n2, c->kd);
+        } else {
+            if (c->q.flagged()) {                         // an earlier scan's wait timed out: one stream from now on
+                const int rc4 = pipe_recover(c);
+                if (rc4 != LO_OK) return rc4;
             }
-            for (int it = 0; it < g.max_iterations; ++it) {
-                const bool tail = it >= pipe_main;
-                if (it == pipe_main)                   // bound 0: the test hook's forced timeout
-                    hipLaunchKernelGGL(k_wait_seq, dim3(1), dim3(kWave), 0, s_tail, fin, seq, c->d_st, c->d_hbroken,
-                                       fail ? 0ull : c->pipe_bound);
-                const hipStream_t s = tail ? s_tail : c->stream;
-                const KParams& Pi = tail ? Pt : (it + 1 == pipe_main ? Ph : P);
-                launch_pko_spec(c, Pi, it, s);
-                if (it + 1 < g.max_iterations) hipLaunchKernelGGL(k_pick_correspond, dim3(P.nb), dim3(kBlock), 0, s, Pi, it);
-                else hipLaunchKernelGGL(k_pick, dim3(1), dim3(kBlock), 0, s, Pi, it);
-            }
-            if (defer && c->n_hold < kMaxLanes) {         // enqueued by a later pipelined scan, or by flush_hold
-                if (c->n_hold == 0) g_holding.fetch_add(1, std::memory_order_relaxed);
-                c->holds[c->n_hold++] = lo_ctx::Hold{seq, lane, c->d_st};
-            } else {
-                const int rcf = flush_hold(c);            // (none pending: a scan that does not defer flushed them above)
-                if (rcf != LO_OK) return rcf;
-                hipLaunchKernelGGL(k_wait_final, dim3(1), dim3(kWave), 0, c->stream, fin, seq, c->d_st, c->d_hbroken,
-                                   c->pipe_bound);
-            }
-            LO_HIP(c, hipGetLastError());
-            if (timed) LO_HIP(c, hipEventRecord(c->ev1, c->stream));
-            c->pending = true;
-            return LO_OK;
-        }
-        const int rcf = flush_hold(c);                    // (none pending unless the pipeline was just switched off)
-        if (rcf != LO_OK) return rcf;
-        for (int it = 0; it < g.max_iterations; ++it) {
-            if (!fused) {
-                if (it == 0) launch_correspond_first(c, P0, c->kd);
-                else launch_correspond(c, P, 0, c->kd);
-                launch_gn_tail(c, P, it);
-                continue;
-            }
-            if (it == 0) {
-                launch_correspond_first(c, P0, c->kd);
-                if (c->exact) launch_exact_scale_any(c, P, n2, c->stream);
-            }
-            launch_pko_spec(c, P, it);
-            if (it + 1 < g.max_iterations && !c->kd) {
-                if (P.cand_rec) hipLaunchKernelGGL(k_pick_correspond, dim3(P.nb), dim3(kBlock), 0, c->stream, P, it);
-                else hipLaunchKernelGGL(k_solve_correspond, dim3(P.nb), dim3(kBlock), 0, c->stream, P, it);
-            } else if (it + 1 < g.max_iterations) {
-                launch_pick_knn(c, P, it);
-            } else if (P.cand_rec) {
-                hipLaunchKernelGGL(k_pick, dim3(1), dim3(kBlock), 0, c->stream, P, it);
-            } else {
-                hipLaunchKernelGGL(k_solve_pick, dim3(1), dim3(kBlock), 0, c->stream, P, it);
-            }
+            // (c->q.pipe as it is now: a recovery just above switched it off, whatever the plan saw)
+            if (plan.pipelined && c->q.pipe) return emit_pipelined(c, plan, P, P0, n2, ring_run);
+            const int rcf = flush_hold(c);                // (none pending unless the pipeline was just switched off)
+            if (rcf != LO_OK) return rcf;
+            emit_single(c, P, P0, n2, fused);
         }
         LO_HIP(c, hipGetLastError());
     }
@@ -581,7 +337,7 @@ int lo_icp_result(lo_ctx* c, float T_out[12], lo_iter_log* logs, lo_stats* st) {
     { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
     // state header + the executed iterations' logs only
     const size_t bytes = offsetof(DevState, logs) + sizeof(lo_iter_log) * static_cast<size_t>(c->cfg.max_iterations);
-    LO_HIP(c, hipMemcpyAsync(c->h_st, c->d_st, bytes, hipMemcpyDeviceToHost, c->stream));
+    LO_HIP(c, hipMemcpyAsync(c->h_st, cur(c).d_st, bytes, hipMemcpyDeviceToHost, c->stream));
     // a device-filtered scan: its count comes back in the same sync (lo_filtered_points(ctx, NULL, 0) then reads it
     // without another round trip -- the frame loop asks for it every frame)
     c->nf_valid = c->last_dev_count && c->vf.n_out;
@@ -602,10 +358,10 @@ int lo_icp_result(lo_ctx* c, float T_out[12], lo_iter_log* logs, lo_stats* st) {
         c->sync_call = timed;
         if (rc == LO_OK) rc = flush_hold(c);
         if (rc != LO_OK) return rc;
-        LO_HIP(c, hipMemcpyAsync(c->h_st, c->d_st, bytes, hipMemcpyDeviceToHost, c->stream));
+        LO_HIP(c, hipMemcpyAsync(c->h_st, cur(c).d_st, bytes, hipMemcpyDeviceToHost, c->stream));
         LO_HIP(c, hipStreamSynchronize(c->stream));
         c->pending = false;
-        ++c->pipe_reruns;
+        ++c->q.pipe_reruns;
         status = hs->status;
     }
     if (c->kd && c->grid_dev && !c->grid.has_order && hs->kd_tie && c->last_n > 0) {
@@ -620,7 +376,7 @@ int lo_icp_result(lo_ctx* c, float T_out[12], lo_iter_log* logs, lo_stats* st) {
         c->sync_call = timed;
         if (rc == LO_OK) rc = flush_hold(c);
         if (rc != LO_OK) return rc;
-        LO_HIP(c, hipMemcpyAsync(c->h_st, c->d_st, bytes, hipMemcpyDeviceToHost, c->stream));
+        LO_HIP(c, hipMemcpyAsync(c->h_st, cur(c).d_st, bytes, hipMemcpyDeviceToHost, c->stream));
         LO_HIP(c, hipStreamSynchronize(c->stream));
         c->pending = false;
         ++c->kd_reruns;
@@ -649,35 +405,6 @@ int lo_icp_result(lo_ctx* c, float T_out[12], lo_iter_log* logs, lo_stats* st) {
 int lo_sync(lo_ctx* c) {
     if (!c) return LO_ERR_ARG;
     LO_HIP(c, sync_all(c));
-    return LO_OK;
-}
-
-int lo_icp_flush(lo_ctx* c) {
-    if (!c) return LO_ERR_ARG;
-    return flush_hold(c);
-}
-
-int lo_icp_queue_records(lo_ctx* c, int n_last, float* out16xN) {
-    if (!c || n_last < 0 || (n_last > 0 && !out16xN)) return LO_ERR_ARG;
-    if (n_last > kRingRecords || static_cast<unsigned>(n_last) > c->ring_n) {
-        c->err = "lo_icp_queue_records: n_last exceeds the ring, or the pipelined scans queued since the last other call";
-        return LO_ERR_ARG;
-    }
-    LO_HIP(c, hipSetDevice(c->device));
-    LO_HIP(c, sync_all(c));                              // the holds, then every stream of the context
-    if (pipe_flagged(c)) {                               // a wait timed out: those scans' records were never written
-        const int rc = pipe_recover(c);
-        return rc != LO_OK ? rc : LO_ERR_PIPELINE;
-    }
-    const unsigned long long first = c->ring_pos - static_cast<unsigned long long>(n_last);
-    // oldest first: the run up to the ring's end, then the wrapped rest
-    const size_t slot = static_cast<size_t>(first % kRingRecords);
-    const size_t run = std::min<size_t>(static_cast<size_t>(n_last), kRingRecords - slot);
-    if (run > 0)
-        LO_HIP(c, hipMemcpy(out16xN, c->d_ring + slot * kRecWords, run * kRecWords * sizeof(float), hipMemcpyDeviceToHost));
-    if (run < static_cast<size_t>(n_last))
-        LO_HIP(c, hipMemcpy(out16xN + run * kRecWords, c->d_ring.get(), (n_last - run) * kRecWords * sizeof(float),
-                            hipMemcpyDeviceToHost));
     return LO_OK;
 }
 
@@ -770,7 +497,7 @@ retry:
             launch_gn_tail(c, P, it);
         }
         LO_HIP(c, hipGetLastError());
-        LO_HIP(c, hipMemcpyAsync(c->h_st, c->d_st, head, hipMemcpyDeviceToHost, c->stream));
+        LO_HIP(c, hipMemcpyAsync(c->h_st, cur(c).d_st, head, hipMemcpyDeviceToHost, c->stream));
         LO_HIP(c, hipStreamSynchronize(c->stream));
         if (c->h_st->done) break;                                 // converged, or too few correspondences
     }
@@ -780,7 +507,7 @@ retry:
     LO_HIP(c, hipGetLastError());
     LO_HIP(c, hipEventRecord(c->ev1, c->stream));
     const size_t bytes = head + sizeof(lo_iter_log) * static_cast<size_t>(LO_MAX_ITERS);
-    LO_HIP(c, hipMemcpyAsync(c->h_st, c->d_st, bytes, hipMemcpyDeviceToHost, c->stream));
+    LO_HIP(c, hipMemcpyAsync(c->h_st, cur(c).d_st, bytes, hipMemcpyDeviceToHost, c->stream));
     LO_HIP(c, hipStreamSynchronize(c->stream));
     if (c->h_st->kd_tie && !with_order) {               // a deciding tie was ranked by index: redo with the order
         with_order = true;
