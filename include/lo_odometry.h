@@ -174,7 +174,9 @@ int       lo_odom_save_map_ply(lo_odometry* o, const char* path, float voxel_siz
  * the same constructor: everything after creation is this one set of calls.  A KDTree loop rebuilds the grids of the
  * sequences that made a keyframe with one lo_batch_sync_points (lo_map.h) directly after their lo_batch_update_maps
  * (RebuildKdTree, Estimator.cpp:460-462), and equals a solo KDTree lo_odometry in the same fields and in lo_kd_reruns.
- * lo_odom_batch_last_error(NULL) says why the calling thread's last create failed.  No loop closure.
+ * lo_odom_batch_last_error(NULL) says why the calling thread's last create failed.  No loop closure in this
+ * loop yet: the batched detector exists (lo_iris_batch.h: the candidates of any subset of sequences in one set of
+ * launches), but it is not wired in here -- that also needs a batched loop ICP.
  * info[j].device_ms is the whole batch's optimize; info[j].map_ms the batched update's enqueue (KDTree: and the grid
  * build with its synchronise). */
 typedef struct lo_odom_batch lo_odom_batch;

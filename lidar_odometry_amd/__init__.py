@@ -8,8 +8,8 @@ from ._lib import LIB_PATH, lib, pinned_empty  # noqa: F401
 from .icp import (AdaptiveMEstimatorConfig, BatchOptimizer, BatchResult, ICPConfig,  # noqa: F401
                   IterativeClosestPointOptimizer, MapGeometry, OptimizationStats)
 from .gmap import GlobalMapBuilder  # noqa: F401
-from .iris import IrisLoopDetector, LoopCandidate, LoopClosureConfig  # noqa: F401
+from .iris import BatchIrisDetector, IrisLoopDetector, LoopCandidate, LoopClosureConfig  # noqa: F401
 
 __all__ = ["IterativeClosestPointOptimizer", "BatchOptimizer", "BatchResult", "ICPConfig", "AdaptiveMEstimatorConfig", "MapGeometry",
-           "OptimizationStats", "IrisLoopDetector", "LoopCandidate", "LoopClosureConfig", "GlobalMapBuilder", "lib",
+           "OptimizationStats", "IrisLoopDetector", "BatchIrisDetector", "LoopCandidate", "LoopClosureConfig", "GlobalMapBuilder", "lib",
            "LIB_PATH"]

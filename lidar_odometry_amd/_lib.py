@@ -59,6 +59,10 @@ EXPORTED_SYMBOLS = (
     "lo_iris_config_default", "lo_iris_create", "lo_iris_destroy", "lo_iris_last_error", "lo_iris_size",
     "lo_iris_capacity", "lo_iris_clear", "lo_iris_image", "lo_iris_encode", "lo_iris_add_keyframe",
     "lo_iris_add_from_scan", "lo_iris_compare_all", "lo_iris_detect", "lo_iris_select_host", "lo_iris_bench_match",
+    # include/lo_iris_batch.h
+    "lo_iris_batch_create", "lo_iris_batch_destroy", "lo_iris_batch_last_error", "lo_iris_batch_size",
+    "lo_iris_batch_capacity", "lo_iris_batch_clear", "lo_iris_batch_add", "lo_iris_batch_add_from_scans",
+    "lo_iris_batch_detect", "lo_iris_batch_compare_all",
     # include/lo_gmap.h
     "lo_gmap_create", "lo_gmap_destroy", "lo_gmap_last_error", "lo_gmap_clear", "lo_gmap_keyframes", "lo_gmap_points",
     "lo_gmap_add_keyframe", "lo_gmap_add_from_scan", "lo_gmap_build", "lo_gmap_download", "lo_gmap_device_points",
@@ -388,6 +392,24 @@ def lib():
     L.lo_iris_select_host.restype = C.c_longlong
     L.lo_iris_select_host.argtypes = [C.POINTER(LoIrisConfig), C.c_int64, fp, i64p, fp, fp, C.c_size_t]
     L.lo_iris_bench_match.argtypes = [vp, C.c_int, fp]
+    jp, stp, vpp = C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(vp)
+    L.lo_iris_batch_create.restype = vp
+    L.lo_iris_batch_create.argtypes = [vp, C.c_size_t, C.POINTER(C.c_int)]
+    L.lo_iris_batch_destroy.restype = None
+    L.lo_iris_batch_destroy.argtypes = [vp]
+    L.lo_iris_batch_last_error.restype = C.c_char_p
+    L.lo_iris_batch_last_error.argtypes = [vp]
+    L.lo_iris_batch_size.restype = C.c_size_t
+    L.lo_iris_batch_size.argtypes = [vp, C.c_int]
+    L.lo_iris_batch_capacity.restype = C.c_size_t
+    L.lo_iris_batch_capacity.argtypes = [vp]
+    L.lo_iris_batch_clear.argtypes = [vp, C.c_int]
+    L.lo_iris_batch_add.argtypes = [vp, jp, C.c_int, i64p, fp, vpp, C.POINTER(C.c_size_t), C.c_int, stp]
+    L.lo_iris_batch_add_from_scans.argtypes = [vp, jp, C.c_int, i64p, fp, stp]
+    L.lo_iris_batch_detect.argtypes = [vp, C.POINTER(LoIrisConfig), jp, C.c_int, i64p, fp, vpp,
+                                       C.POINTER(C.c_size_t), C.c_int, C.POINTER(LoIrisCandidate), stp]
+    L.lo_iris_batch_compare_all.argtypes = [vp, jp, C.c_int, vpp, C.POINTER(C.c_size_t), C.c_int,
+                                            C.POINTER(C.c_size_t), fp, ip, ip, ip, C.c_size_t]
     L.lo_save_ply.restype = C.c_int
     L.lo_save_ply.argtypes = [C.c_char_p, fp, C.c_size_t]
     szp = C.POINTER(C.c_size_t)

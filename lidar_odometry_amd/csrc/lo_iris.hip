@@ -5,12 +5,8 @@
 //   k_iris_encode  image -> the bit-packed descriptor (fp64 circular convolution with the log-Gabor kernels)
 //   k_iris_match   one query descriptor against every database entry at all 360 column shifts, in-block argmin
 //
-// Packed descriptor (kDescWords 64-bit words = 43,200 B): column-major, 15 words per image column:
-//   words 0..4   Re bits  (bit p = r * 4 + s of the column: range row r, scale s -- 320 bits)
-//   words 5..9   Im bits  (same order)
-//   words 10..14 VALID bits = ~M (same order; M's two halves are identical, so one copy serves Re and Im)
-// The 640-row axis lies inside the words, so a circular column shift is an index rotation over whole 120-byte
-// columns, and the row order inside a column (any fixed permutation) does not change a popcount.
+// The packed descriptor's layout and the kernels' device bodies are in lo_iris_body.h, shared with the batched
+// detector (lo_iris_batch.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,182 +21,40 @@
 #include "../../include/lo_iris.h"
 #include "lo_buf.h"
 #include "lo_ctx_internal.h"
+#include "lo_iris_body.h"
 
 namespace lo {
 namespace iris {
 
-constexpr int kRows = LO_IRIS_ROWS;
-constexpr int kCols = LO_IRIS_COLS;
-constexpr int kScales = 4;
-constexpr int kHalfWords = 5;                      // 320 bits
-constexpr int kWords = 3 * kHalfWords;             // per column: Re, Im, valid
-constexpr int kDescWords = kCols * kWords;         // 5400 x 8 B = 43,200 B
-constexpr int kImgWords = kRows * kCols / 4;       // the image as 32-bit words
-constexpr int kThreads = 384;                      // >= kCols, 6 waves
-constexpr int kEntries = 2;                        // database entries per match workgroup (query LDS reads shared)
-static_assert(kRows * kScales == 64 * kHalfWords, "Re / Im / valid halves fill whole words");
-
-// ---------------------------------------------------------------------------------------------------- image
-// LidarIris::GetIris (LidarIris.cpp:4-19).
 __global__ void __launch_bounds__(256) k_iris_image(const float* __restrict__ pts, int n, uint32_t* __restrict__ img) {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const float x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
-        const float dis = sqrtf(x * x + y * y);
-        const float yaw = static_cast<float>(static_cast<double>(atan2f(y, x) * 180.0f) / M_PI + 180.0);
-        // clamped in floating point first: the reference's int casts of out-of-range values are only defined there
-        const int q_dis = static_cast<int>(fminf(fmaxf(floorf(dis), 0.0f), static_cast<float>(kRows - 1)));
-        const int q_arc = static_cast<int>(fminf(fmaxf(ceilf(z + 5.0f), 0.0f), 7.0f));
-        const int q_yaw = static_cast<int>(fmin(fmax(floor(static_cast<double>(yaw) + 0.5), 0.0),
-                                                static_cast<double>(kCols - 1)));
-        const int cell = q_dis * kCols + q_yaw;            // < kRows * kCols by the clamps
-        atomicOr(&img[cell >> 2], (1u << q_arc) << (8 * (cell & 3)));
-    }
+    image_points(pts, n, img, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
 
-// ---------------------------------------------------------------------------------------------------- encode
-// LogGaborFilter + LoGFeatureEncode (LidarIris.cpp:84-154) for image row blockIdx.x and scale blockIdx.y.
-// idft(dft(x) . F_s) is the circular convolution of x with h_s = idft(F_s) (unscaled, as cv::idft without DFT_SCALE);
-// h (4 x 360 complex, fp64) is built on the host, so one pass of 360 x 360 real-by-complex products per (row, scale)
-// gives the response directly; zero cells (most of an iris image) are skipped, which is exact.
+// image row blockIdx.x, scale blockIdx.y
 __global__ void __launch_bounds__(kThreads) k_iris_encode(const uint32_t* __restrict__ img,
                                                           const double2* __restrict__ h,
                                                           uint32_t* __restrict__ desc) {
-    __shared__ double sx[kCols];
-    __shared__ double2 sh[kCols];
-    const int r = blockIdx.x, s = blockIdx.y, t = threadIdx.x;
-    if (t < kCols) {
-        const int cell = r * kCols + t;
-        sx[t] = static_cast<double>((img[cell >> 2] >> (8 * (cell & 3))) & 0xffu);
-        sh[t] = h[s * kCols + t];
-    }
-    __syncthreads();
-    if (t >= kCols) return;
-    double re = 0.0, im = 0.0;
-    int d = t;                                             // (t - m) mod 360
-    for (int m = 0; m < kCols; ++m) {
-        const double xm = sx[m];
-        if (xm != 0.0) {                                   // block-uniform
-            const double2 hv = sh[d];
-            re += xm * hv.x;
-            im += xm * hv.y;
-        }
-        d = d == 0 ? kCols - 1 : d - 1;
-    }
-    const int p = r * kScales + s;                         // bit inside the column's 320-bit half
-    const uint32_t bit = 1u << (p & 31);
-    uint32_t* col = desc + static_cast<size_t>(t) * (2 * kWords) + (p >> 5);
-    if (re > 0.0) atomicOr(col, bit);
-    if (im > 0.0) atomicOr(col + 2 * kHalfWords, bit);
-    if (!(sqrt(re * re + im * im) < 1e-4)) atomicOr(col + 4 * kHalfWords, bit);
+    encode_row(img, h, desc, blockIdx.x, blockIdx.y);
 }
 
-// ---------------------------------------------------------------------------------------------------- match
-// LidarIris::GetHammingDistance (LidarIris.cpp:164-193) at every shift.  One workgroup = kEntries database entries x
-// all 360 shifts: thread s holds shift s, walks the 360 columns, reads the query's column (c - s) mod 360 from LDS
-// (word-major there: consecutive shifts read consecutive 8-byte words, no bank conflict) and the entries' column c
-// through wave-uniform addresses.  total = 2 popcount(valid1 & valid2) (the mask counts for both halves); the
-// block's argmin over s orders by (distance, s), NaN last.
-__device__ inline int popc64(uint64_t v) { return __popcll(v); }
-
+// One workgroup = database entries blockIdx.x * kEntries ... (past the end: the last one again, not written) x all
+// 360 shifts.
 __global__ void __launch_bounds__(kThreads) k_iris_match(const uint64_t* __restrict__ db,
                                                          const uint64_t* __restrict__ q, int n_db,
                                                          float* __restrict__ out_dist, int* __restrict__ out_bias,
                                                          int* __restrict__ out_diff, int* __restrict__ out_total) {
-    __shared__ uint64_t sq[kWords * kCols];
-    __shared__ unsigned long long skey[kThreads];
-    const int t = threadIdx.x;
-    for (int i = t; i < kDescWords; i += kThreads) sq[(i % kWords) * kCols + i / kWords] = q[i];
-    __syncthreads();
     const int e0 = blockIdx.x * kEntries;
     const uint64_t* ent[kEntries];
 #pragma unroll
     for (int j = 0; j < kEntries; ++j) ent[j] = db + static_cast<size_t>(min(e0 + j, n_db - 1)) * kDescWords;
-    const int s = t < kCols ? t : 0;
-    int idx = s == 0 ? 0 : kCols - s;                      // (c - s) mod 360 at c = 0
-    int diff[kEntries], val[kEntries];
-#pragma unroll
-    for (int j = 0; j < kEntries; ++j) diff[j] = val[j] = 0;
-    for (int c = 0; c < kCols; ++c) {
-        uint64_t qw[kWords];
-#pragma unroll
-        for (int w = 0; w < kWords; ++w) qw[w] = sq[w * kCols + idx];
-#pragma unroll
-        for (int j = 0; j < kEntries; ++j) {
-            const uint64_t* d = ent[j] + c * kWords;
-#pragma unroll
-            for (int w = 0; w < kHalfWords; ++w) {
-                const uint64_t v = qw[2 * kHalfWords + w] & d[2 * kHalfWords + w];
-                val[j] += popc64(v);
-                diff[j] += popc64((qw[w] ^ d[w]) & v) + popc64((qw[kHalfWords + w] ^ d[kHalfWords + w]) & v);
-            }
-        }
-        idx = idx + 1 == kCols ? 0 : idx + 1;
-    }
-#pragma unroll
-    for (int j = 0; j < kEntries; ++j) {
-        const int total = 2 * val[j];
-        const float dist = static_cast<float>(diff[j]) / static_cast<float>(total);   // total = 0: 0 / 0, unused
-        // distances are >= +0, so their bit patterns order as the values do; NaN (total = 0) sorts last
-        unsigned long long key = ~0ull;
-        if (t < kCols)
-            key = (static_cast<unsigned long long>(total ? __float_as_uint(dist) : 0xffffffffu) << 32) |
-                  static_cast<unsigned>(t);
-        __syncthreads();
-        skey[t] = key;
-        __syncthreads();
-        for (int off = 256; off > 0; off >>= 1) {
-            if (t < off && t + off < kThreads) skey[t] = min(skey[t], skey[t + off]);
-            __syncthreads();
-        }
-        const unsigned long long best = skey[0];
+    match_block(q, ent, [&](int j, float dist, int bias, int diff, int total) {
         const int e = e0 + j;
-        if (e < n_db) {
-            if ((best >> 32) == 0xffffffffull) {           // every shift fully masked
-                if (t == 0) {
-                    out_dist[e] = __uint_as_float(0x7fc00000u);
-                    out_bias[e] = -1;
-                    out_diff[e] = 0;
-                    out_total[e] = 0;
-                }
-            } else if (t == static_cast<int>(best & 0xffffffffull)) {
-                out_dist[e] = dist;
-                out_bias[e] = t;
-                out_diff[e] = diff[j];
-                out_total[e] = total;
-            }
-        }
-    }
-}
-
-// The four log-Gabor kernels h_s = idft(F_s), unscaled: F_s[0] = 0, F_s[k] = exp(-ln^2((k / 360) / fo) / (2 ln^2 sigma))
-// for k = 1..180 with fo = 1 / wavelength, F_s[181..359] = 0; wavelength 18, x mult per scale (LidarIris.cpp:95-130
-// with the detector's nscale 4, minWaveLength 18, mult 2.1f, sigmaOnf 0.75f).
-static void build_kernels(std::vector<double>& h) {
-    h.assign(static_cast<size_t>(kScales) * kCols * 2, 0.0);
-    const long double two_pi = 2.0L * acosl(-1.0L);
-    const double mult = static_cast<double>(2.1f), sigma = static_cast<double>(0.75f);
-    const double den = 2.0 * std::log(sigma) * std::log(sigma);
-    double wavelength = 18.0;
-    for (int s = 0; s < kScales; ++s) {
-        const double fo = 1.0 / wavelength;
-        long double F[kCols / 2 + 1];
-        F[0] = 0.0L;
-        for (int k = 1; k <= kCols / 2; ++k) {
-            const double l = std::log((static_cast<double>(k) / kCols) / fo);
-            F[k] = std::exp(-(l * l) / den);
-        }
-        for (int d = 0; d < kCols; ++d) {
-            long double re = 0.0L, im = 0.0L;
-            for (int k = 1; k <= kCols / 2; ++k) {
-                const long double a = two_pi * static_cast<long double>((k * d) % kCols) / kCols;
-                re += F[k] * cosl(a);
-                im += F[k] * sinl(a);
-            }
-            h[(static_cast<size_t>(s) * kCols + d) * 2] = static_cast<double>(re);
-            h[(static_cast<size_t>(s) * kCols + d) * 2 + 1] = static_cast<double>(im);
-        }
-        wavelength *= mult;
-    }
+        if (e >= n_db) return;
+        out_dist[e] = dist;
+        out_bias[e] = bias;
+        out_diff[e] = diff;
+        out_total[e] = total;
+    });
 }
 
 }  // namespace iris
@@ -438,18 +292,11 @@ int lo_iris_compare_all(lo_iris* m, const float* pts, size_t n, int on_device, f
 long long lo_iris_select_host(const lo_iris_config* cfg, int64_t current_id, const float current_position[3],
                               const int64_t* ids, const float* positions, const float* dist, size_t n) {
     if (!cfg || !current_position || (n > 0 && (!ids || !positions || !dist))) return -1;
-    long long best = -1;
-    for (size_t i = 0; i < n; ++i) {
-        if (static_cast<int>(current_id) - static_cast<int>(ids[i]) < cfg->min_keyframe_gap) continue;
-        const float dx = current_position[0] - positions[3 * i], dy = current_position[1] - positions[3 * i + 1],
-                    dz = current_position[2] - positions[3 * i + 2];
-        const float d = std::sqrt(dx * dx + dy * dy + dz * dz);
-        if (d > cfg->max_search_distance) continue;
-        if (std::isnan(dist[i])) continue;
-        if (best < 0 || dist[i] < dist[best]) best = static_cast<long long>(i);
-    }
-    if (best >= 0 && dist[best] > cfg->similarity_threshold) best = -1;
-    return best;
+    Best best;                                             // the rule itself: lo_iris_body.h
+    for (size_t i = 0; i < n; ++i)
+        if (eligible(*cfg, current_id, current_position, ids[i], positions + 3 * i))
+            best.offer(static_cast<long long>(i), dist[i]);
+    return best.pick(*cfg);
 }
 
 int lo_iris_detect(lo_iris* m, const lo_iris_config* cfg, int64_t id, const float position[3], const float* pts,

@@ -193,3 +193,138 @@ class IrisLoopDetector:
         ms = C.c_float(0.0)
         self._check(self._L.lo_iris_bench_match(self._h, int(reps), C.byref(ms)))
         return float(ms.value)
+
+
+class BatchIrisDetector:
+    """One LiDAR-Iris database per job of a ``BatchOptimizer`` behind one handle (``include/lo_iris_batch.h``).
+
+    The keyframes of any subset of jobs are added, and the queries of any subset of jobs are answered, in one set of
+    launches on the batch stream.  Per job every result equals an ``IrisLoopDetector`` on that job's context, bit for
+    bit.  ``jobs`` lists distinct job indices; ``ids``, ``positions`` and ``clouds`` follow the list's order.  The
+    clouds of one call are all numpy arrays or all device tensors."""
+
+    def __init__(self, batch_optimizer, capacity: int, config: LoopClosureConfig | None = None):
+        self.config = config or LoopClosureConfig()
+        self._L = lib()
+        self._owner = batch_optimizer                # the batch must outlive the detector
+        err = C.c_int(0)
+        self._h = self._L.lo_iris_batch_create(getattr(batch_optimizer, "_b", batch_optimizer), int(capacity),
+                                               C.byref(err))
+        if not self._h:
+            raise RuntimeError(f"lo_iris_batch_create failed (code {err.value})")
+
+    def close(self):
+        h = getattr(self, "_h", None)
+        if h:
+            self._h = None
+            self._L.lo_iris_batch_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, statuses=()):
+        # a negative code that no job reports is the whole call's
+        if rc < 0 and rc not in statuses:
+            raise RuntimeError(f"liblo_icp error {rc}: {self._L.lo_iris_batch_last_error(self._h).decode()}")
+        return rc
+
+    @property
+    def capacity(self) -> int:
+        return int(self._L.lo_iris_batch_capacity(self._h))
+
+    def size(self, job: int) -> int:
+        return int(self._L.lo_iris_batch_size(self._h, int(job)))
+
+    def clear(self, job: int | None = None):
+        self._check(self._L.lo_iris_batch_clear(self._h, -1 if job is None else int(job)))
+
+    @staticmethod
+    def _jobs(jobs):
+        j = np.ascontiguousarray(jobs, dtype=np.int32).reshape(-1)
+        return j, j.ctypes.data_as(C.POINTER(C.c_int))
+
+    @staticmethod
+    def _keys(k, ids, positions):
+        i = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        p = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        if len(i) != k or len(p) != k:
+            raise ValueError(f"need {k} ids and positions")
+        return i, p
+
+    @staticmethod
+    def _clouds(k, clouds):
+        """-> (keepalive, pointer array, count array, on_device)."""
+        if len(clouds) != k:
+            raise ValueError(f"need {k} clouds")
+        c = [_cloud(p) for p in clouds]
+        dev = {x[3] for x in c if x[2] > 0}
+        if len(dev) > 1:
+            raise ValueError("the clouds of one call are all host arrays or all device tensors")
+        ptrs = (C.c_void_p * max(k, 1))(*[x[1] if x[2] > 0 else None for x in c])
+        ns = (C.c_size_t * max(k, 1))(*[x[2] for x in c])
+        return c, ptrs, ns, (dev.pop() if dev else 0)
+
+    # ------------------------------------------------------------------ database
+    def add(self, jobs, ids, positions, clouds):
+        """lo_iris_batch_add: one status per listed job -- LO_OK, LO_INSUFFICIENT (an empty cloud: nothing added) or
+        LO_ERR_CAPACITY (that job's database is full)."""
+        j, jp = self._jobs(jobs)
+        i, p = self._keys(len(j), ids, positions)
+        keep, ptrs, ns, dev = self._clouds(len(j), clouds)
+        st = np.zeros(max(len(j), 1), np.int32)
+        rc = self._L.lo_iris_batch_add(self._h, jp, len(j), i.ctypes.data_as(C.POINTER(C.c_int64)), _fptr(p), ptrs, ns,
+                                       dev, st.ctypes.data_as(C.POINTER(C.c_int)))
+        del keep
+        st = [int(s) for s in st[:len(j)]]
+        self._check(rc, st)
+        return st
+
+    def add_from_scans(self, jobs, ids, positions):
+        """lo_iris_batch_add_from_scans: the listed jobs' device-filtered scans (``BatchOptimizer.filter_raw``) as
+        their keyframes' clouds; statuses as ``add``."""
+        j, jp = self._jobs(jobs)
+        i, p = self._keys(len(j), ids, positions)
+        st = np.zeros(max(len(j), 1), np.int32)
+        rc = self._L.lo_iris_batch_add_from_scans(self._h, jp, len(j), i.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                  _fptr(p), st.ctypes.data_as(C.POINTER(C.c_int)))
+        st = [int(s) for s in st[:len(j)]]
+        self._check(rc, st)
+        return st
+
+    # ------------------------------------------------------------------ matching
+    def detect(self, jobs, ids, positions, clouds=None, config: LoopClosureConfig | None = None):
+        """lo_iris_batch_detect: a ``LoopCandidate`` or None per listed job (the keyframes are not added).
+        clouds=None: the jobs' device-filtered scans."""
+        j, jp = self._jobs(jobs)
+        i, p = self._keys(len(j), ids, positions)
+        keep, ptrs, ns, dev = (None, None, None, 1) if clouds is None else self._clouds(len(j), clouds)
+        cfg = (config or self.config).to_c()
+        cand = (LoIrisCandidate * max(len(j), 1))()
+        st = np.full(max(len(j), 1), LO_INSUFFICIENT, np.int32)
+        rc = self._L.lo_iris_batch_detect(self._h, C.byref(cfg), jp, len(j), i.ctypes.data_as(C.POINTER(C.c_int64)),
+                                          _fptr(p), ptrs, ns, dev, cand, st.ctypes.data_as(C.POINTER(C.c_int)))
+        del keep
+        self._check(rc)
+        return [LoopCandidate(int(c.query_keyframe_id), int(c.match_keyframe_id), float(c.distance), int(c.bias))
+                if s == LO_OK else None for c, s in zip(cand, st[:len(j)])]
+
+    def compare_all(self, jobs, clouds):
+        """lo_iris_batch_compare_all, ungated: per listed job (distance float32, bias, diff, total int32 arrays) over
+        its database in insertion order; empty arrays for an empty query cloud."""
+        j, jp = self._jobs(jobs)
+        keep, ptrs, ns, dev = self._clouds(len(j), clouds)
+        cap = sum(self.size(x) for x in j)
+        off = np.zeros(len(j) + 1, np.uintp)
+        dist = np.zeros(max(cap, 1), np.float32)
+        bias, diff, total = (np.zeros(max(cap, 1), np.int32) for _ in range(3))
+        ip = C.POINTER(C.c_int32)
+        self._check(self._L.lo_iris_batch_compare_all(self._h, jp, len(j), ptrs, ns, dev,
+                                                      off.ctypes.data_as(C.POINTER(C.c_size_t)), _fptr(dist),
+                                                      bias.ctypes.data_as(ip), diff.ctypes.data_as(ip),
+                                                      total.ctypes.data_as(ip), cap))
+        del keep
+        self.last_offsets = [int(o) for o in off]
+        return [tuple(a[int(off[x]):int(off[x + 1])].copy() for a in (dist, bias, diff, total)) for x in range(len(j))]
