@@ -494,6 +494,10 @@ long long lo_debug_live_bytes(void);
  * when start_cap (words) or pts_cap (points) is too small.  An all-pairs grid has no cells: no start words. */
 int lo_debug_grid(lo_ctx* ctx, float* h, int org[3], int dim[3], int* m, uint32_t* start, size_t start_cap, float* pts4,
                   size_t pts_cap);
+/* Diagnostic (tests): the same for the loop-closure ICP's local map of the matched cloud, as the last
+ * lo_icp_optimize_loop / lo_icp_optimize_loop_dev left it (any context mode). */
+int lo_debug_loop_grid(lo_ctx* ctx, float* h, int org[3], int dim[3], int* m, uint32_t* start, size_t start_cap,
+                       float* pts4, size_t pts_cap);
 /* Context-free host variant (no GPU needed): sample_size = gmm_sample_size. */
 int lo_pko_sample_indices_host(size_t n, int sample_size, int32_t* out);
 

@@ -44,7 +44,9 @@ struct PointGrid {
     float h = 1.0f;
 };
 
-// grid_from_device's scratch: the bounds readback, keys / values (and their sorted copies), cell counts, hipCUB temp.
+// The device grid builder's scratch per context (lo_grid.hip; the solo and the batched form share it): the bounds
+// readback, each point's cell / arrival number / slot (d_keys: 3 words per point), the cell counts, and the solo
+// scan's chunk sums (a batch keeps its own for all jobs).
 // d_bounds / h_bounds hold kGridWords 4-byte words: [0..5] the bounds, [6] the raw count, then
 constexpr int kGridOcc = 7;        // occupied cells (the min_per_cell rule)
 constexpr int kGridBad = 8;        // a non-finite world point (k_cloud_world)
@@ -55,7 +57,7 @@ struct DevGridScratch {
     PinnedBuf<float> h_bounds;
     DevBuf<uint32_t> d_keys;
     DevBuf<uint32_t> d_counts;
-    DevBuf<unsigned char> d_tmp;
+    DevBuf<uint32_t> d_bsum;
 };
 
 struct lo_ctx {

@@ -1,23 +1,16 @@
 // lo_grid.hip — the KDTree variant's point grid: built on the host (grid_build, all_pairs_upload; lo_map_set_points)
-// or on the device (grid_from_device and its k_grid_* kernels: a device map's centroids through ctx_grid_from_device,
-// the loop-closure ICP's device-resident matched cloud through loop_map_from_device; the grids of all active jobs of a
-// KDTree batch through batch_grids_from_device and its k_grid_*_b kernels: eight launches, lo_batch_sync_points).
-#include <hipcub/hipcub.hpp>
-
+// or on the device by one builder with two shells (the k_grid_* kernels: grid_from_device for one context -- a device
+// map's centroids through ctx_grid_from_device, the loop-closure ICP's device-resident matched cloud through
+// loop_map_from_device -- and batch_grids_from_device for all active jobs of a KDTree batch, lo_batch_sync_points).
+// The geometry all three share is lo_grid_geom.h.
 #include "lo_ctx_def.h"
-
-// VoxelMap::RebuildKdTree (VoxelMap.cpp:420-438) equivalent: a dense uniform grid (cell = 2 x voxel, doubled
-// until it fits kKdMaxCells) over the L0 centroids in GetPointCloud order; points sorted by cell (x fastest),
-// index order inside a cell; kd_start[cell] = first point, kd_start[ncell] = m.
-static constexpr size_t kKdMaxCells = size_t(1) << 26;
+#include "lo_grid_geom.h"
 
 namespace lo {
+// The host builder (lo_grid_geom.h has the layout and the geometry).
 // with_order: also the reference kd-tree's visit order (the tie-break of equal distances); without it the kNN
 // kernels flag a deciding tie in DevState::kd_tie instead of ranking it (the loop-closure ICP then rebuilds with it).
-// min_per_cell > 0 (the loop-closure ICP's matched keyframe cloud): the cell edge doubles (up to 3 times) while the
-// occupied cells hold fewer than min_per_cell points on average -- a voxel-filtered, strided keyframe cloud is sparse
-// at 2 x voxel_size, so most queries would need the outer shells or the brute-force fallback.  The kNN result does
-// not depend on the edge (every answer is certified against the scanned cube); only the work per query does.
+// min_per_cell > 0 (the loop-closure ICP's matched keyframe cloud): the occupancy rule, grid_widen.
 int grid_build(lo_ctx* c, PointGrid& G, const float* xyz, size_t m, bool with_order, int min_per_cell) {
     if (m > 0 && !xyz) { c->err = "null points"; return LO_ERR_ARG; }
     if (m > static_cast<size_t>(INT32_MAX / 2)) { c->err = "too many map points"; return LO_ERR_CAPACITY; }
@@ -30,39 +23,29 @@ int grid_build(lo_ctx* c, PointGrid& G, const float* xyz, size_t m, bool with_or
     std::vector<uint32_t> vpos;
     std::thread order_thread([&] { if (with_order) KdOrderBuilder(xyz, m).build(nodes, vpos); });
     struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{order_thread};
+    float bounds[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    for (size_t i = 0; i < m; ++i)
+        for (int a = 0; a < 3; ++a) {
+            bounds[a] = std::min(bounds[a], xyz[3 * i + a]);
+            bounds[3 + a] = std::max(bounds[3 + a], xyz[3 * i + a]);
+        }
     float h = 2.0f * c->cfg.voxel_size;
     int org[3] = {0, 0, 0}, dim[3] = {1, 1, 1};
-    auto cell = [&](float v) { return static_cast<int64_t>(std::floor(v / h)); };
     std::vector<uint32_t> start, lin(m);
+    size_t ncell = 1;
     for (int grow = 0;; ++grow) {
-    for (;;) {
-        int64_t lo[3] = {INT64_MAX, INT64_MAX, INT64_MAX}, hi[3] = {INT64_MIN, INT64_MIN, INT64_MIN};
-        for (size_t i = 0; i < m; ++i)
-            for (int a = 0; a < 3; ++a) { const int64_t k = cell(xyz[3 * i + a]); lo[a] = std::min(lo[a], k); hi[a] = std::max(hi[a], k); }
-        if (m == 0) { for (int a = 0; a < 3; ++a) { lo[a] = 0; hi[a] = 0; } }
-        size_t ncell = 1;
-        bool ok = true;
-        for (int a = 0; a < 3; ++a) {
-            const int64_t d = hi[a] - lo[a] + 1;
-            if (d > static_cast<int64_t>(kKdMaxCells) || lo[a] < INT32_MIN / 2 || hi[a] > INT32_MAX / 2) { ok = false; break; }
-            ncell *= static_cast<size_t>(d);
-            if (ncell > kKdMaxCells) { ok = false; break; }
+        ncell = grid_fit(bounds, m, h, org, dim);
+        start.assign(ncell + 1, 0);
+        size_t occupied = 0;
+        for (size_t i = 0; i < m; ++i) {
+            const int64_t x = grid_cell(xyz[3 * i], h) - org[0], y = grid_cell(xyz[3 * i + 1], h) - org[1],
+                          z = grid_cell(xyz[3 * i + 2], h) - org[2];
+            lin[i] = static_cast<uint32_t>((static_cast<size_t>(z) * dim[1] + y) * dim[0] + x);
+            occupied += start[lin[i] + 1]++ == 0;
         }
-        if (ok) { for (int a = 0; a < 3; ++a) { org[a] = static_cast<int>(lo[a]); dim[a] = static_cast<int>(hi[a] - lo[a] + 1); } break; }
+        if (!grid_widen(min_per_cell, grow, m, occupied)) break;
         h *= 2.0f;
     }
-    const size_t ncell = static_cast<size_t>(dim[0]) * dim[1] * dim[2];
-    start.assign(ncell + 1, 0);
-    size_t occupied = 0;
-    for (size_t i = 0; i < m; ++i) {
-        const int64_t x = cell(xyz[3 * i]) - org[0], y = cell(xyz[3 * i + 1]) - org[1], z = cell(xyz[3 * i + 2]) - org[2];
-        lin[i] = static_cast<uint32_t>((static_cast<size_t>(z) * dim[1] + y) * dim[0] + x);
-        occupied += start[lin[i] + 1]++ == 0;
-    }
-    if (min_per_cell > 0 && grow < 3 && m >= 64 && occupied * static_cast<size_t>(min_per_cell) > m) { h *= 2.0f; continue; }
-    break;
-    }
-    const size_t ncell = static_cast<size_t>(dim[0]) * dim[1] * dim[2];
     for (size_t k = 0; k < ncell; ++k) start[k + 1] += start[k];
     std::vector<float4> pts(std::max<size_t>(m, 1));
     std::vector<uint32_t> fill(start.begin(), start.end() - 1);
@@ -136,17 +119,61 @@ int all_pairs_upload(lo_ctx* c, PointGrid& G, const float* xyz, size_t m, const 
     G.all = true;
     return LO_OK;
 }
-}  // namespace lo
 
-namespace lo {
-// ---- the same grid built on the device (ctx_grid_from_device: the device map's L0 centroids) ----
-// Every kernel here clamps the device count to the array's capacity: a corrupt or overflowing count is reported by the
-// host (out[6] carries the raw count) without a read past the array.
-// the bounds of one point array by one 1024-thread workgroup: out[0..2] the minima, [3..5] the maxima, [6] the raw count
-__device__ __forceinline__ void grid_bounds_body(const float* __restrict__ xyz, const int* __restrict__ d_count, int cap,
-                                                 float* __restrict__ out) {
+// ---- the same grid built on the device: one builder, a solo and a batch shell around every kernel body ----
+// grid_from_device builds one grid on the context stream, its job's descriptor (GridJob) passed to the k_grid_*_1
+// shells by value; batch_grids_from_device builds the grids of all active jobs on the batch stream, the k_grid_*_b
+// shells reading descriptor blockIdx.y of a device array.  Either way: a bounds launch, seven words per job read back
+// with the call's one synchronise, the geometry on the host (grid_fit), and seven launches (grid_emit):
+//   clear       counts[0 .. ncell] = 0
+//   keys        every point's cell, and its arrival number in the cell (the cell count's atomicAdd)
+//   scan_sum    exclusive scan of counts into start, three launches: each workgroup sums its chunk of the job's
+//   scan_top      ncell + 1 counts, one workgroup per job scans the chunk sums, each workgroup scans its chunk from
+//   scan_write    its offset
+//   claim       slots[start[cell] + arrival] = point index (arrival order inside a cell: arbitrary)
+//   place       a point's rank in its cell = the cell's slot entries with a smaller index; the point goes to
+//               start[cell] + rank -- index order inside a cell, whatever order the atomics landed in
+// Every phase reads what an earlier launch wrote: no kernel fills through atomics and reads the result itself.  Every
+// kernel clamps the device count to the array's capacity and to the host's copy that sized the buffers (grid_job_m):
+// the host reports a corrupt or overflowing count (the bounds' seventh word) and nothing reads or writes past an array.
+struct GridGeom {
+    float h;
+    int org[3], dim[3];
+};
+// point i's cell in the grid, x fastest (grid_build's lin[i])
+__device__ __forceinline__ uint32_t grid_lin(const float* __restrict__ xyz, int i, const GridGeom& g) {
+    const long long x = grid_cell(xyz[3 * i], g.h) - g.org[0], y = grid_cell(xyz[3 * i + 1], g.h) - g.org[1],
+                    z = grid_cell(xyz[3 * i + 2], g.h) - g.org[2];
+    return static_cast<uint32_t>((static_cast<unsigned long long>(z) * g.dim[1] + y) * g.dim[0] + x);
+}
+struct GridJob {
+    const float* xyz;                // the points, 3 floats each
+    const int* d_count;              //   *d_count of them on the device (clamped to cap and to m)
+    int cap;
+    int m;                           // the host's copy of the count (what the buffers below are sized for)
+    GridGeom g;
+    uint32_t n;                      // ncell + 1: the words of counts and start
+    uint32_t chunk;                  // scan: words per workgroup (a multiple of kGridScanBlock)
+    uint32_t* counts;                // [n]
+    uint32_t* start;                 // [n]
+    uint32_t* keys;                  // [m] a point's cell (kGridNoCell: none)
+    uint32_t* rank;                  // [m] its arrival number in the cell
+    uint32_t* slots;                 // [m] point indices grouped by cell
+    uint32_t* bsum;                  // [gridDim.x of the scan] chunk sums, then their exclusive scan
+    uint32_t* occ;                   // nullable: counts the occupied cells (the occupancy rule; zeroed by the host)
+    float4* pts;                     // [m]
+};
+constexpr int kGridScanBlock = 256;
+constexpr int kGridScanMaxBlocks = 1024;         // chunk sums per job: what scan_top's one workgroup scans
+constexpr int kGridBatchWGs = 65536;             // workgroups per launch over all jobs
+constexpr uint32_t kGridNoCell = 0xFFFFFFFFu;
+__device__ __forceinline__ int grid_job_m(const GridJob& J) { return min(min(max(*J.d_count, 0), J.cap), J.m); }
+// The bodies: blk of nblk workgroups work on job J.  Bounds, by one 1024-thread workgroup: out[0..2] the minima,
+// [3..5] the maxima, [6] the raw count.
+__device__ __forceinline__ void grid_bounds_body(const GridJob& J, float* __restrict__ out) {
     __shared__ float s[6][16];
-    const int m_raw = *d_count, m = min(max(m_raw, 0), cap), tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const float* __restrict__ xyz = J.xyz;
+    const int m_raw = *J.d_count, m = min(max(m_raw, 0), J.cap), tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (int i = tid; i < m; i += 1024)
         for (int a = 0; a < 3; ++a) { const float v = xyz[3 * i + a]; lo[a] = fminf(lo[a], v); hi[a] = fmaxf(hi[a], v); }
@@ -161,139 +188,262 @@ __device__ __forceinline__ void grid_bounds_body(const float* __restrict__ xyz, 
     }
     if (tid == 0) out[6] = __int_as_float(m_raw);
 }
-__global__ __launch_bounds__(1024) void k_grid_bounds(const float* __restrict__ xyz, const int* __restrict__ d_count,
-                                                     int cap, float* __restrict__ out) {
-    grid_bounds_body(xyz, d_count, cap, out);
+__device__ __forceinline__ void grid_clear_body(const GridJob& J, uint32_t blk, uint32_t nblk) {
+    const uint32_t n4 = J.n >> 2, step = nblk * 256u;
+    uint4* c4 = reinterpret_cast<uint4*>(J.counts);      // (a hipMalloc'ed array: 16-byte aligned)
+    for (uint32_t k = blk * 256u + threadIdx.x; k < n4; k += step) c4[k] = make_uint4(0u, 0u, 0u, 0u);
+    if (blk == 0 && threadIdx.x < (J.n & 3u)) J.counts[4u * n4 + threadIdx.x] = 0u;
 }
-struct GridGeom {
-    float h;
-    int org[3], dim[3];
-};
-// grid_build's cell of a coordinate: floor(v / h) in fp32, as an int64 (the same operations)
-__device__ __forceinline__ long long grid_cell(float v, float h) { return static_cast<long long>(floorf(v / h)); }
-// point i's cell in the grid, x fastest (grid_build's lin[i])
-__device__ __forceinline__ uint32_t grid_lin(const float* __restrict__ xyz, int i, const GridGeom& g) {
-    const long long x = grid_cell(xyz[3 * i], g.h) - g.org[0], y = grid_cell(xyz[3 * i + 1], g.h) - g.org[1],
-                    z = grid_cell(xyz[3 * i + 2], g.h) - g.org[2];
-    return static_cast<uint32_t>((static_cast<unsigned long long>(z) * g.dim[1] + y) * g.dim[0] + x);
-}
-// occ (nullable): the number of occupied cells (grid_build's `occupied`, for the min_per_cell rule)
-__global__ void k_grid_keys(const float* __restrict__ xyz, const int* __restrict__ d_count, int cap, GridGeom g,
-                            uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t* __restrict__ counts,
-                            uint32_t* __restrict__ occ) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= min(*d_count, cap)) return;
-    const uint32_t lin = grid_lin(xyz, i, g);
-    keys[i] = lin;
-    vals[i] = static_cast<uint32_t>(i);
-    if (atomicAdd(&counts[lin], 1u) == 0u && occ) atomicAdd(occ, 1u);
-}
-__global__ void k_grid_scatter(const float* __restrict__ xyz, const int* __restrict__ d_count, int cap,
-                               const uint32_t* __restrict__ svals, float4* __restrict__ pts) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= min(*d_count, cap)) return;
-    const uint32_t i = svals[p];
-    pts[p] = make_float4(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], __int_as_float(static_cast<int>(i)));
-}
-
-// The scratch words behind the six bounds and the count (DevGridScratch::d_bounds / h_bounds, kGridWords floats).
-int grid_scratch(lo_ctx* c) {
-    LO_HIP(c, c->gscr.d_bounds.reserve(kGridWords));
-    LO_HIP(c, c->gscr.h_bounds.reserve(kGridWords));
-    return LO_OK;
-}
-
-// grid_build's geometry loop from the bounds of m points (floor(v / h) is monotone in v, so the cells' extremes are the
-// extremes' cells): h doubles until the grid fits kKdMaxCells; org / dim out; returns the cell count.
-static size_t grid_fit(const float* bounds, size_t m, float& h, int org[3], int dim[3]) {
-    auto cell = [&](float v) { return static_cast<int64_t>(std::floor(v / h)); };
-    for (;;) {
-        int64_t lo[3], hi[3];
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = m ? cell(bounds[a]) : 0;
-            hi[a] = m ? cell(bounds[3 + a]) : 0;
+// A cell outside the grid cannot come from the points the bounds were taken of; such a point (a non-finite
+// coordinate, say) is left out instead of counted.
+__device__ __forceinline__ void grid_keys_body(const GridJob& J, int blk, int nblk) {
+    const int m = grid_job_m(J), step = nblk * 256;
+    for (int i = blk * 256 + threadIdx.x; i < m; i += step) {
+        uint32_t lin = grid_lin(J.xyz, i, J.g), r = 0u;
+        if (lin < J.n - 1u) {
+            r = atomicAdd(&J.counts[lin], 1u);
+            if (r == 0u && J.occ) atomicAdd(J.occ, 1u);      // grid_build's `occupied`
+        } else {
+            lin = kGridNoCell;
         }
-        size_t ncell = 1;
-        bool ok = true;
-        for (int a = 0; a < 3; ++a) {
-            const int64_t d = hi[a] - lo[a] + 1;
-            if (d > static_cast<int64_t>(kKdMaxCells) || lo[a] < INT32_MIN / 2 || hi[a] > INT32_MAX / 2) { ok = false; break; }
-            ncell *= static_cast<size_t>(d);
-            if (ncell > kKdMaxCells) { ok = false; break; }
-        }
-        if (ok) {
-            for (int a = 0; a < 3; ++a) { org[a] = static_cast<int>(lo[a]); dim[a] = static_cast<int>(hi[a] - lo[a] + 1); }
-            return ncell;
-        }
-        h *= 2.0f;
+        J.keys[i] = lin;
+        J.rank[i] = r;
+    }
+}
+// exclusive scan of one value per thread over a 64 * NW-thread workgroup; total: the workgroup's sum
+template <int NW>
+__device__ __forceinline__ uint32_t grid_block_scan(uint32_t v, uint32_t* s_w, uint32_t& total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t inc = v;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t t = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += t;
+    }
+    if (lane == 63) s_w[w] = inc;
+    __syncthreads();
+    uint32_t off = 0u, tot = 0u;
+    for (int k = 0; k < NW; ++k) {
+        const uint32_t t = s_w[k];
+        if (k < w) off += t;
+        tot += t;
+    }
+    __syncthreads();                                     // s_w is free for the next call
+    total = tot;
+    return off + inc - v;
+}
+__device__ __forceinline__ void grid_scan_sum_body(const GridJob& J, uint32_t blk) {
+    __shared__ uint32_t s_w[kGridScanBlock / 64];
+    const uint64_t b0 = static_cast<uint64_t>(blk) * J.chunk;
+    const uint32_t e0 = static_cast<uint32_t>(min(b0 + J.chunk, static_cast<uint64_t>(J.n)));
+    uint32_t sum = 0u;
+    for (uint64_t k = b0 + threadIdx.x; k < e0; k += kGridScanBlock) sum += J.counts[k];
+    uint32_t total;
+    (void)grid_block_scan<kGridScanBlock / 64>(sum, s_w, total);
+    if (threadIdx.x == 0) J.bsum[blk] = total;
+}
+__device__ __forceinline__ void grid_scan_top_body(const GridJob& J, int nblk) {
+    __shared__ uint32_t s_w[kGridScanMaxBlocks / 64];
+    const int t = threadIdx.x;
+    const uint32_t v = t < nblk ? J.bsum[t] : 0u;
+    uint32_t total;
+    const uint32_t ex = grid_block_scan<kGridScanMaxBlocks / 64>(v, s_w, total);
+    if (t < nblk) J.bsum[t] = ex;
+}
+__device__ __forceinline__ void grid_scan_write_body(const GridJob& J, uint32_t blk) {
+    __shared__ uint32_t s_w[kGridScanBlock / 64];
+    const uint64_t b0 = static_cast<uint64_t>(blk) * J.chunk;
+    if (b0 >= J.n) return;                               // (the whole workgroup: no barrier is skipped by a part of it)
+    const uint32_t e0 = static_cast<uint32_t>(min(b0 + J.chunk, static_cast<uint64_t>(J.n)));
+    uint32_t carry = J.bsum[blk];
+    for (uint32_t base = static_cast<uint32_t>(b0); base < e0; base += kGridScanBlock) {
+        const uint32_t k = base + threadIdx.x;
+        const uint32_t v = k < e0 ? J.counts[k] : 0u;
+        uint32_t total;
+        const uint32_t ex = grid_block_scan<kGridScanBlock / 64>(v, s_w, total);
+        if (k < e0) J.start[k] = carry + ex;
+        carry += total;
+    }
+}
+__device__ __forceinline__ void grid_claim_body(const GridJob& J, int blk, int nblk) {
+    const int m = grid_job_m(J), step = nblk * 256;
+    for (int i = blk * 256 + threadIdx.x; i < m; i += step) {
+        const uint32_t lin = J.keys[i];
+        if (lin == kGridNoCell) continue;
+        const uint32_t p = J.start[lin] + J.rank[i];
+        if (p < static_cast<uint32_t>(m)) J.slots[p] = static_cast<uint32_t>(i);
+    }
+}
+__device__ __forceinline__ void grid_place_body(const GridJob& J, int blk, int nblk) {
+    const int m = grid_job_m(J), step = nblk * 256;
+    for (int i = blk * 256 + threadIdx.x; i < m; i += step) {
+        const uint32_t lin = J.keys[i];
+        if (lin == kGridNoCell) continue;
+        const uint32_t s = J.start[lin], e = min(J.start[lin + 1u], static_cast<uint32_t>(m));
+        uint32_t p = s;
+        for (uint32_t q = s; q < e; ++q) p += J.slots[q] < static_cast<uint32_t>(i) ? 1u : 0u;
+        if (p < static_cast<uint32_t>(m))
+            J.pts[p] = make_float4(J.xyz[3 * i], J.xyz[3 * i + 1], J.xyz[3 * i + 2], __int_as_float(i));
     }
 }
 
-// grid_build's grid of a device point array, into G.  min_per_cell as grid_build: the cell edge doubles (up to 3
-// times) while the occupied cells hold fewer points on average -- the occupied count is one more 4-byte readback per
-// doubling step.
+// The shells.  _1: one job, by value; _b: blockIdx.y = active slot, its job's descriptor read from a device array.
+__global__ __launch_bounds__(1024) void k_grid_bounds_1(GridJob J, float* __restrict__ out) { grid_bounds_body(J, out); }
+__global__ __launch_bounds__(1024) void k_grid_bounds_b(const GridJob* __restrict__ jobs, float* __restrict__ out) {
+    grid_bounds_body(jobs[blockIdx.y], out + 7 * blockIdx.y);
+}
+__global__ __launch_bounds__(256) void k_grid_clear_1(GridJob J) { grid_clear_body(J, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(256)
+void k_grid_clear_b(const GridJob* __restrict__ jobs) { grid_clear_body(jobs[blockIdx.y], blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(256) void k_grid_keys_1(GridJob J) { grid_keys_body(J, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(256)
+void k_grid_keys_b(const GridJob* __restrict__ jobs) { grid_keys_body(jobs[blockIdx.y], blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(kGridScanBlock) void k_grid_scan_sum_1(GridJob J) { grid_scan_sum_body(J, blockIdx.x); }
+__global__ __launch_bounds__(kGridScanBlock)
+void k_grid_scan_sum_b(const GridJob* __restrict__ jobs) { grid_scan_sum_body(jobs[blockIdx.y], blockIdx.x); }
+__global__ __launch_bounds__(kGridScanMaxBlocks) void k_grid_scan_top_1(GridJob J, int nblk) { grid_scan_top_body(J, nblk); }
+__global__ __launch_bounds__(kGridScanMaxBlocks)
+void k_grid_scan_top_b(const GridJob* __restrict__ jobs, int nblk) { grid_scan_top_body(jobs[blockIdx.y], nblk); }
+__global__ __launch_bounds__(kGridScanBlock) void k_grid_scan_write_1(GridJob J) { grid_scan_write_body(J, blockIdx.x); }
+__global__ __launch_bounds__(kGridScanBlock)
+void k_grid_scan_write_b(const GridJob* __restrict__ jobs) { grid_scan_write_body(jobs[blockIdx.y], blockIdx.x); }
+__global__ __launch_bounds__(256) void k_grid_claim_1(GridJob J) { grid_claim_body(J, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(256)
+void k_grid_claim_b(const GridJob* __restrict__ jobs) { grid_claim_body(jobs[blockIdx.y], blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(256) void k_grid_place_1(GridJob J) { grid_place_body(J, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(256)
+void k_grid_place_b(const GridJob* __restrict__ jobs) { grid_place_body(jobs[blockIdx.y], blockIdx.x, gridDim.x); }
+
+// ---- the host side both forms share ----
+// the scratch words behind the six bounds and the count (kGridWords floats), and the solo scan's chunk sums
+int grid_scratch(lo_ctx* c) {
+    LO_HIP(c, c->gscr.d_bounds.reserve(kGridWords));
+    LO_HIP(c, c->gscr.h_bounds.reserve(kGridWords));
+    LO_HIP(c, c->gscr.d_bsum.reserve(kGridScanMaxBlocks));
+    return LO_OK;
+}
+// A buffer that has to grow takes half as much again (at most 4M elements more): a map gains cells and points with
+// every keyframe, and a hipFree + hipMalloc per buffer per job per keyframe costs more than the eight launches (their
+// cost rises with the number of live allocations: B = 1024 keyframes took 256 ms with exact sizes).
+template <class T>
+static hipError_t grid_grow(DevBuf<T>& buf, size_t need) {
+    return need <= buf.capacity() ? hipSuccess : buf.reserve(need + std::min(need / 2, size_t(1) << 22));
+}
+// a job over a device point array whose count is on the device too; the count in its bounds readback (raw)
+static GridJob grid_job_of(const float* xyz, const int* d_count, size_t cap) {
+    GridJob J{};
+    J.xyz = xyz;
+    J.d_count = d_count;
+    J.cap = static_cast<int>(std::min(cap, static_cast<size_t>(INT32_MAX)));
+    return J;
+}
+static size_t grid_count(const float* hb) {
+    int mi = 0;
+    std::memcpy(&mi, &hb[6], sizeof(int));
+    return static_cast<size_t>(std::max(mi, 0));
+}
+// Job J bound to grid G of m points in ncell cells: G's and the scratch's buffers grown where they have to (nothing in
+// flight may read them), the descriptor's geometry and pointers, and G's host fields as the launches will leave it.
+static hipError_t grid_job_bind(GridJob& J, PointGrid& G, DevGridScratch& W, size_t m, size_t ncell, const GridGeom& g) {
+    const size_t mm = std::max<size_t>(m, 1);
+    hipError_t e = grid_grow(G.d_pts, mm);
+    if (e == hipSuccess) e = grid_grow(G.d_start, ncell + 1);
+    if (e == hipSuccess) e = grid_grow(W.d_keys, 3 * mm);    // keys, rank, slots
+    if (e == hipSuccess) e = grid_grow(W.d_counts, ncell + 1);
+    if (e != hipSuccess) return e;
+    J.m = G.m = static_cast<int>(m);
+    J.g = g;
+    J.n = static_cast<uint32_t>(ncell + 1);
+    J.counts = W.d_counts;
+    J.start = G.d_start;
+    J.keys = W.d_keys;
+    J.rank = J.keys + mm;
+    J.slots = J.rank + mm;
+    J.pts = G.d_pts;
+    G.has_order = G.all = false;
+    G.h = g.h;
+    for (int a = 0; a < 3; ++a) { G.org[a] = g.org[a]; G.dim[a] = g.dim[a]; }
+    return hipSuccess;
+}
+// One set of launches: over the batch's k descriptors on the device (d_jobs; the _b shells), or over one job by value
+// (one; the _1 shells: no descriptor upload).
+struct GridRun {
+    hipStream_t stream;
+    const GridJob* d_jobs;
+    const GridJob* one;
+    int k;
+    unsigned pblk, cblk, nblk;       // workgroups per job: over the points, over the counts (clear), scan chunks
+};
+// launch sizes from the largest job (max_m points, max_n count words) under the workgroup budget; the scan's chunk
+// count is common to all jobs
+static GridRun grid_run(hipStream_t stream, const GridJob* d_jobs, const GridJob* one, int k, size_t max_m, size_t max_n) {
+    const unsigned per_job = static_cast<unsigned>(std::max(1, kGridBatchWGs / k));
+    auto blocks = [&](size_t items, size_t per) {
+        return static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>(per_job, (items + per - 1) / per)));
+    };
+    return GridRun{stream, d_jobs, one, k, blocks(max_m, 256), blocks(max_n, 16 * 256),
+                   std::min(blocks(max_n, 8 * kGridScanBlock), static_cast<unsigned>(kGridScanMaxBlocks))};
+}
+// a job's chunk of the scan's nblk, and where its chunk sums go
+static void grid_job_scan(GridJob& J, unsigned nblk, uint32_t* bsum) {
+    const uint32_t per = (J.n + nblk - 1) / nblk;
+    J.chunk = (per + kGridScanBlock - 1) / kGridScanBlock * kGridScanBlock;
+    J.bsum = bsum;
+}
+template <class KB, class K1, class... A>
+static void grid_launch(const GridRun& R, KB kb, K1 k1, unsigned blocks, unsigned threads, A... a) {
+    if (R.d_jobs) hipLaunchKernelGGL(kb, dim3(blocks, R.k), dim3(threads), 0, R.stream, R.d_jobs, a...);
+    else hipLaunchKernelGGL(k1, dim3(blocks), dim3(threads), 0, R.stream, *R.one, a...);
+}
+// The launch list.  kGridBin alone is what the occupancy rule repeats per cell edge it tries.
+enum { kGridBin = 1, kGridOrder = 2 };
+static void grid_emit(const GridRun& R, int phases) {
+    if (phases & kGridBin) {
+        grid_launch(R, k_grid_clear_b, k_grid_clear_1, R.cblk, 256);
+        grid_launch(R, k_grid_keys_b, k_grid_keys_1, R.pblk, 256);
+    }
+    if (phases & kGridOrder) {
+        grid_launch(R, k_grid_scan_sum_b, k_grid_scan_sum_1, R.nblk, kGridScanBlock);
+        grid_launch(R, k_grid_scan_top_b, k_grid_scan_top_1, 1, kGridScanMaxBlocks, static_cast<int>(R.nblk));
+        grid_launch(R, k_grid_scan_write_b, k_grid_scan_write_1, R.nblk, kGridScanBlock);
+        grid_launch(R, k_grid_claim_b, k_grid_claim_1, R.pblk, 256);
+        grid_launch(R, k_grid_place_b, k_grid_place_1, R.pblk, 256);
+    }
+}
+
+// grid_build's grid of a device point array, into G, on the context stream.  min_per_cell as grid_build: while the
+// rule can still ask (grid_widen), keys counts the occupied cells and the count is one more 4-byte readback.
 int grid_from_device(lo_ctx* c, PointGrid& G, const float* d_xyz, const int* d_count, size_t cap, int min_per_cell) {
     DevGridScratch& S = c->gscr;
     int rc = grid_scratch(c);
     if (rc != LO_OK) return rc;
-    const int capi = static_cast<int>(std::min(cap, static_cast<size_t>(INT32_MAX)));
-    hipLaunchKernelGGL(k_grid_bounds, dim3(1), dim3(1024), 0, c->stream, d_xyz, d_count, capi, S.d_bounds);
+    GridJob J = grid_job_of(d_xyz, d_count, cap);
+    hipLaunchKernelGGL(k_grid_bounds_1, dim3(1), dim3(1024), 0, c->stream, J, S.d_bounds.get());
     LO_HIP(c, hipMemcpyAsync(S.h_bounds, S.d_bounds, 7 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     LO_HIP(c, hipStreamSynchronize(c->stream));
-    int mi = 0;
-    std::memcpy(&mi, &S.h_bounds[6], sizeof(int));
-    const size_t m = static_cast<size_t>(std::max(mi, 0));
+    const size_t m = grid_count(S.h_bounds);
     if (m > cap) { c->err = "ctx_grid_from_device: count beyond the array"; return LO_ERR_CAPACITY; }
-    float h = 2.0f * c->cfg.voxel_size;
-    int org[3] = {0, 0, 0}, dim[3] = {1, 1, 1};
-    const size_t mm = std::max<size_t>(m, 1);
-    LO_HIP(c, G.d_pts.reserve(mm));
-    LO_HIP(c, S.d_keys.reserve(4 * mm));                 // keys, vals, sorted keys, sorted vals
-    uint32_t *keys = S.d_keys, *vals = keys + mm, *skeys = vals + mm, *svals = skeys + mm;
     uint32_t* d_occ = reinterpret_cast<uint32_t*>(S.d_bounds.get()) + kGridOcc;
-    const dim3 grid((mm + 255) / 256), blk(256);
-    size_t ncell = 1;
+    GridGeom g{2.0f * c->cfg.voxel_size, {0, 0, 0}, {1, 1, 1}};
+    GridRun R{};
     for (int grow = 0;; ++grow) {
-        ncell = grid_fit(S.h_bounds, m, h, org, dim);
-        LO_HIP(c, G.d_start.reserve(ncell + 1));
-        LO_HIP(c, S.d_counts.reserve(ncell + 1));
-        LO_HIP(c, hipMemsetAsync(S.d_counts, 0, (ncell + 1) * sizeof(uint32_t), c->stream));
-        const bool sparse_rule = min_per_cell > 0 && grow < 3 && m >= 64;
-        if (sparse_rule) LO_HIP(c, hipMemsetAsync(d_occ, 0, sizeof(uint32_t), c->stream));
-        const GridGeom g{h, {org[0], org[1], org[2]}, {dim[0], dim[1], dim[2]}};
-        if (m > 0)
-            hipLaunchKernelGGL(k_grid_keys, grid, blk, 0, c->stream, d_xyz, d_count, capi, g, keys, vals, S.d_counts.get(),
-                               sparse_rule ? d_occ : nullptr);
-        if (!sparse_rule) break;
+        const size_t ncell = grid_fit(S.h_bounds, m, g.h, g.org, g.dim);
+        LO_HIP(c, grid_job_bind(J, G, S, m, ncell, g));
+        R = grid_run(c->stream, nullptr, &J, 1, std::max<size_t>(m, 1), ncell + 1);
+        grid_job_scan(J, R.nblk, S.d_bsum);
+        const bool rule = grid_widen(min_per_cell, grow, m, m);
+        J.occ = rule ? d_occ : nullptr;
+        if (rule) LO_HIP(c, hipMemsetAsync(d_occ, 0, sizeof(uint32_t), c->stream));
+        grid_emit(R, kGridBin);
+        if (!rule) break;
         LO_HIP(c, hipMemcpyAsync(S.h_bounds + kGridOcc, d_occ, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         LO_HIP(c, hipStreamSynchronize(c->stream));
         uint32_t occupied = 0;
         std::memcpy(&occupied, &S.h_bounds[kGridOcc], sizeof(uint32_t));
-        if (static_cast<size_t>(occupied) * static_cast<size_t>(min_per_cell) > m) { h *= 2.0f; continue; }
-        break;
+        if (!grid_widen(min_per_cell, grow, m, occupied)) break;
+        g.h *= 2.0f;
     }
-    int bits = 1;
-    while (bits < 32 && (size_t(1) << bits) < ncell) ++bits;
-    size_t tmp_sort = 0, tmp_scan = 0;
-    LO_HIP(c, hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_sort, keys, skeys, vals, svals, static_cast<int>(mm), 0, bits,
-                                                 c->stream));
-    LO_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_scan, S.d_counts.get(), G.d_start.get(), static_cast<int>(ncell + 1),
-                                               c->stream));
-    LO_HIP(c, S.d_tmp.reserve(std::max(tmp_sort, tmp_scan)));
-    if (m > 0) {
-        size_t t = S.d_tmp.capacity();
-        LO_HIP(c, hipcub::DeviceRadixSort::SortPairs(S.d_tmp, t, keys, skeys, vals, svals, static_cast<int>(m), 0, bits,
-                                                     c->stream));
-        hipLaunchKernelGGL(k_grid_scatter, grid, blk, 0, c->stream, d_xyz, d_count, capi, svals, G.d_pts.get());
-    }
-    size_t t2 = S.d_tmp.capacity();                           // start[cell] = points in the cells before it; start[ncell] = m
-    LO_HIP(c, hipcub::DeviceScan::ExclusiveSum(S.d_tmp, t2, S.d_counts.get(), G.d_start.get(), static_cast<int>(ncell + 1), c->stream));
+    grid_emit(R, kGridOrder);
     LO_HIP(c, hipGetLastError());
-    G.m = static_cast<int>(m);
-    G.has_order = false;
-    G.all = false;
-    G.h = h;
-    for (int a = 0; a < 3; ++a) { G.org[a] = org[a]; G.dim[a] = dim[a]; }
     return LO_OK;
 }
 
@@ -367,148 +517,8 @@ int ctx_grid_from_device(lo_ctx* c, const float* d_xyz, const int* d_count, size
 }
 
 // ---- the grids of a batch (lo_batch_sync_points): ctx_grid_from_device for all active jobs in one set of launches ----
-// k_grid_*_b: blockIdx.y = active slot, its job's descriptor read from a device array.  Two host-to-device copies (the
-// jobs' point arrays before the bounds, the grids' descriptors after the readback), one device-to-host copy of seven
-// words per job with the call's one synchronise, and eight launches, whatever the number of jobs:
-//   k_grid_bounds_b      one workgroup per job: grid_bounds_body
-//   k_grid_clear_b       counts[0 .. ncell] = 0
-//   k_grid_keys_b        every point's cell, and its arrival number in the cell (the cell count's atomicAdd)
-//   k_grid_scan_sum_b    exclusive scan of counts into start, three launches: each workgroup sums its chunk of the
-//   k_grid_scan_top_b      job's ncell + 1 counts, one workgroup per job scans the chunk sums, each workgroup scans
-//   k_grid_scan_write_b    its chunk from its offset
-//   k_grid_claim_b       slots[start[cell] + arrival] = point index (arrival order inside a cell: arbitrary)
-//   k_grid_place_b       a point's rank in its cell = the cell's slot entries with a smaller index; the point goes to
-//                        start[cell] + rank -- index order inside a cell, whatever order the atomics landed in
-// Every phase reads what an earlier launch wrote: no kernel fills through atomics and reads the result itself.
-struct GridJob {
-    const float* xyz;                // the points, 3 floats each
-    const int* d_count;              //   *d_count of them on the device (clamped to cap and to m)
-    int cap;
-    int m;                           // the host's copy of the count (what the buffers below are sized for)
-    GridGeom g;
-    uint32_t n;                      // ncell + 1: the words of counts and start
-    uint32_t chunk;                  // scan: words per workgroup (a multiple of kGridScanBlock)
-    uint32_t* counts;                // [n]
-    uint32_t* start;                 // [n]
-    uint32_t* keys;                  // [m] a point's cell (kGridNoCell: none)
-    uint32_t* rank;                  // [m] its arrival number in the cell
-    uint32_t* slots;                 // [m] point indices grouped by cell
-    uint32_t* bsum;                  // [gridDim.x of the scan] chunk sums, then their exclusive scan
-    float4* pts;                     // [m]
-};
-constexpr int kGridScanBlock = 256;
-constexpr int kGridScanMaxBlocks = 1024;         // chunk sums per job: what k_grid_scan_top_b's one workgroup scans
-constexpr int kGridBatchWGs = 65536;             // workgroups per launch over all jobs
-constexpr uint32_t kGridNoCell = 0xFFFFFFFFu;
-
-__device__ __forceinline__ int grid_job_m(const GridJob& J) { return min(min(max(*J.d_count, 0), J.cap), J.m); }
-
-__global__ __launch_bounds__(1024) void k_grid_bounds_b(const GridJob* __restrict__ jobs, float* __restrict__ out) {
-    const GridJob& J = jobs[blockIdx.y];
-    grid_bounds_body(J.xyz, J.d_count, J.cap, out + 7 * blockIdx.y);
-}
-__global__ __launch_bounds__(256) void k_grid_clear_b(const GridJob* __restrict__ jobs) {
-    const GridJob& J = jobs[blockIdx.y];
-    const uint32_t n4 = J.n >> 2, step = gridDim.x * 256u;
-    uint4* c4 = reinterpret_cast<uint4*>(J.counts);      // (a hipMalloc'ed array: 16-byte aligned)
-    for (uint32_t k = blockIdx.x * 256u + threadIdx.x; k < n4; k += step) c4[k] = make_uint4(0u, 0u, 0u, 0u);
-    if (blockIdx.x == 0 && threadIdx.x < (J.n & 3u)) J.counts[4u * n4 + threadIdx.x] = 0u;
-}
-// k_grid_keys' body per job (no occupancy rule: min_per_cell is 0 here).  A cell outside the grid cannot come from the
-// points the bounds were taken of; such a point (a non-finite coordinate, say) is left out instead of counted.
-__global__ __launch_bounds__(256) void k_grid_keys_b(const GridJob* __restrict__ jobs) {
-    const GridJob& J = jobs[blockIdx.y];
-    const int m = grid_job_m(J), step = gridDim.x * 256;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < m; i += step) {
-        uint32_t lin = grid_lin(J.xyz, i, J.g), r = 0u;
-        if (lin < J.n - 1u) r = atomicAdd(&J.counts[lin], 1u);
-        else lin = kGridNoCell;
-        J.keys[i] = lin;
-        J.rank[i] = r;
-    }
-}
-// exclusive scan of one value per thread over a 64 * NW-thread workgroup; total: the workgroup's sum
-template <int NW>
-__device__ __forceinline__ uint32_t grid_block_scan(uint32_t v, uint32_t* s_w, uint32_t& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    uint32_t off = 0u, tot = 0u;
-    for (int k = 0; k < NW; ++k) {
-        const uint32_t t = s_w[k];
-        if (k < w) off += t;
-        tot += t;
-    }
-    __syncthreads();                                     // s_w is free for the next call
-    total = tot;
-    return off + inc - v;
-}
-__global__ __launch_bounds__(kGridScanBlock) void k_grid_scan_sum_b(const GridJob* __restrict__ jobs) {
-    __shared__ uint32_t s_w[kGridScanBlock / 64];
-    const GridJob& J = jobs[blockIdx.y];
-    const uint64_t b0 = static_cast<uint64_t>(blockIdx.x) * J.chunk;
-    const uint32_t e0 = static_cast<uint32_t>(min(b0 + J.chunk, static_cast<uint64_t>(J.n)));
-    uint32_t sum = 0u;
-    for (uint64_t k = b0 + threadIdx.x; k < e0; k += kGridScanBlock) sum += J.counts[k];
-    uint32_t total;
-    (void)grid_block_scan<kGridScanBlock / 64>(sum, s_w, total);
-    if (threadIdx.x == 0) J.bsum[blockIdx.x] = total;
-}
-__global__ __launch_bounds__(kGridScanMaxBlocks) void k_grid_scan_top_b(const GridJob* __restrict__ jobs, int nblk) {
-    __shared__ uint32_t s_w[kGridScanMaxBlocks / 64];
-    const GridJob& J = jobs[blockIdx.y];
-    const int t = threadIdx.x;
-    const uint32_t v = t < nblk ? J.bsum[t] : 0u;
-    uint32_t total;
-    const uint32_t ex = grid_block_scan<kGridScanMaxBlocks / 64>(v, s_w, total);
-    if (t < nblk) J.bsum[t] = ex;
-}
-__global__ __launch_bounds__(kGridScanBlock) void k_grid_scan_write_b(const GridJob* __restrict__ jobs) {
-    __shared__ uint32_t s_w[kGridScanBlock / 64];
-    const GridJob& J = jobs[blockIdx.y];
-    const uint64_t b0 = static_cast<uint64_t>(blockIdx.x) * J.chunk;
-    if (b0 >= J.n) return;                               // (the whole workgroup: no barrier is skipped by a part of it)
-    const uint32_t e0 = static_cast<uint32_t>(min(b0 + J.chunk, static_cast<uint64_t>(J.n)));
-    uint32_t carry = J.bsum[blockIdx.x];
-    for (uint32_t base = static_cast<uint32_t>(b0); base < e0; base += kGridScanBlock) {
-        const uint32_t k = base + threadIdx.x;
-        const uint32_t v = k < e0 ? J.counts[k] : 0u;
-        uint32_t total;
-        const uint32_t ex = grid_block_scan<kGridScanBlock / 64>(v, s_w, total);
-        if (k < e0) J.start[k] = carry + ex;
-        carry += total;
-    }
-}
-__global__ __launch_bounds__(256) void k_grid_claim_b(const GridJob* __restrict__ jobs) {
-    const GridJob& J = jobs[blockIdx.y];
-    const int m = grid_job_m(J), step = gridDim.x * 256;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < m; i += step) {
-        const uint32_t lin = J.keys[i];
-        if (lin == kGridNoCell) continue;
-        const uint32_t p = J.start[lin] + J.rank[i];
-        if (p < static_cast<uint32_t>(m)) J.slots[p] = static_cast<uint32_t>(i);
-    }
-}
-__global__ __launch_bounds__(256) void k_grid_place_b(const GridJob* __restrict__ jobs) {
-    const GridJob& J = jobs[blockIdx.y];
-    const int m = grid_job_m(J), step = gridDim.x * 256;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < m; i += step) {
-        const uint32_t lin = J.keys[i];
-        if (lin == kGridNoCell) continue;
-        const uint32_t s = J.start[lin], e = min(J.start[lin + 1u], static_cast<uint32_t>(m));
-        uint32_t p = s;
-        for (uint32_t q = s; q < e; ++q) p += J.slots[q] < static_cast<uint32_t>(i) ? 1u : 0u;
-        if (p < static_cast<uint32_t>(m))
-            J.pts[p] = make_float4(J.xyz[3 * i], J.xyz[3 * i + 1], J.xyz[3 * i + 2], __int_as_float(i));
-    }
-}
-
-namespace {
+// Two host-to-device copies (the jobs' point arrays before the bounds, the grids' descriptors after the readback), one
+// device-to-host copy of seven words per job with the call's one synchronise, and eight launches.
 struct BatchGrids {
     int device = 0;
     DevBuf<GridJob> d_jobs;
@@ -519,22 +529,16 @@ struct BatchGrids {
     hipEvent_t ev_up = nullptr;      // the last call's second upload has read h_jobs
     bool up_pending = false;
 };
-void bg_release(void* p) {
+static void bg_release(void* p) {
     BatchGrids* S = static_cast<BatchGrids*>(p);
     (void)hipSetDevice(S->device);
     if (S->ev_up) (void)hipEventDestroy(S->ev_up);
     delete S;
 }
-struct GridErr { std::string err; };
-// A buffer that has to grow takes half as much again (at most 4M elements more): a map gains cells and points with
-// every keyframe, and a hipFree + hipMalloc per buffer per job per keyframe costs more than the eight launches (their
-// cost rises with the number of live allocations: B = 1024 keyframes took 256 ms with exact sizes).
-template <class T>
-hipError_t bg_grow(DevBuf<T>& buf, size_t need) {
-    return need <= buf.capacity() ? hipSuccess : buf.reserve(need + std::min(need / 2, size_t(1) << 22));
-}
 
-int bg_run(lo_batch* b, const GridSrc* src, int n, GridErr* e, int* bad_job) {
+int batch_grids_from_device(lo_batch* b, const GridSrc* src, int n, std::string* err, int* bad_job) {
+    struct Err { std::string err, *out; ~Err() { if (out) *out = err; } } err_{{}, err}, *e = &err_;   // LO_HIP's handle
+    if (bad_job) *bad_job = -1;
     const BatchView V = batch_view(b);
     LO_HIP(e, hipSetDevice(V.device));
     void** slot = batch_grid_state(b, bg_release);
@@ -556,13 +560,7 @@ int bg_run(lo_batch* b, const GridSrc* src, int n, GridErr* e, int* bad_job) {
     }
     if (n <= 0) return LO_OK;
     hipStream_t bs = static_cast<hipStream_t>(V.stream);
-    for (int a = 0; a < n; ++a) {
-        GridJob J{};
-        J.xyz = src[a].xyz;
-        J.d_count = src[a].count;
-        J.cap = static_cast<int>(std::min(src[a].cap, static_cast<size_t>(INT32_MAX)));
-        S->h_jobs[a] = J;
-    }
+    for (int a = 0; a < n; ++a) S->h_jobs[a] = grid_job_of(src[a].xyz, src[a].count, src[a].cap);
     LO_HIP(e, hipMemcpyAsync(S->d_jobs, S->h_jobs, sizeof(GridJob) * n, hipMemcpyHostToDevice, bs));
     hipLaunchKernelGGL(k_grid_bounds_b, dim3(1, n), dim3(1024), 0, bs, S->d_jobs.get(), S->d_bounds.get());
     LO_HIP(e, hipGetLastError());
@@ -575,102 +573,37 @@ int bg_run(lo_batch* b, const GridSrc* src, int n, GridErr* e, int* bad_job) {
     for (int a = 0; a < n; ++a) {
         lo_ctx* c = src[a].c;
         const float* hb = S->h_bounds + 7 * a;
-        int mi = 0;
-        std::memcpy(&mi, &hb[6], sizeof(int));
-        const size_t m = static_cast<size_t>(std::max(mi, 0));
+        const size_t m = grid_count(hb);
         if (m > src[a].cap) {
             c->err = "ctx_grid_from_device: count beyond the array";
             if (rc == LO_OK) {
                 rc = LO_ERR_CAPACITY;
-                *bad_job = src[a].job;
+                if (bad_job) *bad_job = src[a].job;
                 e->err = "job " + std::to_string(src[a].job) + ": " + c->err;
             }
             continue;
         }
-        PointGrid& G = c->grid;
-        DevGridScratch& W = c->gscr;
-        float h = 2.0f * c->cfg.voxel_size;
-        int org[3] = {0, 0, 0}, dim[3] = {1, 1, 1};
-        const size_t ncell = grid_fit(hb, m, h, org, dim), mm = std::max<size_t>(m, 1);
-        LO_HIP(e, bg_grow(G.d_pts, mm));
-        LO_HIP(e, bg_grow(G.d_start, ncell + 1));
-        LO_HIP(e, bg_grow(W.d_keys, 4 * mm));                // (grid_from_device's size: the two forms share it)
-        LO_HIP(e, bg_grow(W.d_counts, ncell + 1));
+        GridGeom g{2.0f * c->cfg.voxel_size, {0, 0, 0}, {1, 1, 1}};
+        const size_t ncell = grid_fit(hb, m, g.h, g.org, g.dim);
         GridJob J = S->h_jobs[a];
-        J.m = static_cast<int>(m);
-        J.g = GridGeom{h, {org[0], org[1], org[2]}, {dim[0], dim[1], dim[2]}};
-        J.n = static_cast<uint32_t>(ncell + 1);
-        J.counts = W.d_counts;
-        J.start = G.d_start;
-        J.keys = W.d_keys;
-        J.rank = J.keys + mm;
-        J.slots = J.rank + mm;
-        J.pts = G.d_pts;
+        LO_HIP(e, grid_job_bind(J, c->grid, c->gscr, m, ncell, g));
         S->h_jobs[k++] = J;                                  // (k <= a: entry a has been read)
         max_n = std::max(max_n, ncell + 1);
-        max_m = std::max(max_m, mm);
-        G.m = static_cast<int>(m);
-        G.has_order = false;
-        G.all = false;
-        G.h = h;
-        for (int x = 0; x < 3; ++x) { G.org[x] = org[x]; G.dim[x] = dim[x]; }
+        max_m = std::max(max_m, m);
         c->grid_dev = true;
     }
     if (k == 0) return rc;
-    // launch sizes from the largest job under the workgroup budget; the scan's chunk count is common to all jobs
-    const unsigned per_job = static_cast<unsigned>(std::max(1, kGridBatchWGs / k));
-    auto blocks = [&](size_t items, size_t per) {
-        return static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>(per_job, (items + per - 1) / per)));
-    };
-    const unsigned nblk = std::min(blocks(max_n, 8 * kGridScanBlock), static_cast<unsigned>(kGridScanMaxBlocks));
+    const GridRun R = grid_run(bs, S->d_jobs, nullptr, k, max_m, max_n);
     LO_HIP(e, S->d_bsum.reserve(std::max(static_cast<size_t>(kGridBatchWGs), B)));      // >= nblk * k
-    for (int a = 0; a < k; ++a) {
-        GridJob& J = S->h_jobs[a];
-        const uint32_t per = (J.n + nblk - 1) / nblk;
-        J.chunk = (per + kGridScanBlock - 1) / kGridScanBlock * kGridScanBlock;
-        J.bsum = S->d_bsum + static_cast<size_t>(a) * nblk;
-    }
+    for (int a = 0; a < k; ++a) grid_job_scan(S->h_jobs[a], R.nblk, S->d_bsum + static_cast<size_t>(a) * R.nblk);
     LO_HIP(e, hipMemcpyAsync(S->d_jobs, S->h_jobs, sizeof(GridJob) * k, hipMemcpyHostToDevice, bs));
     LO_HIP(e, hipEventRecord(S->ev_up, bs));
     S->up_pending = true;
-    const GridJob* J = S->d_jobs;
-    const dim3 pgrid(blocks(max_m, 256), k), cgrid(blocks(max_n, 16 * 256), k), sgrid(nblk, k), blk(256);
-    hipLaunchKernelGGL(k_grid_clear_b, cgrid, blk, 0, bs, J);
-    hipLaunchKernelGGL(k_grid_keys_b, pgrid, blk, 0, bs, J);
-    hipLaunchKernelGGL(k_grid_scan_sum_b, sgrid, dim3(kGridScanBlock), 0, bs, J);
-    hipLaunchKernelGGL(k_grid_scan_top_b, dim3(1, k), dim3(kGridScanMaxBlocks), 0, bs, J, static_cast<int>(nblk));
-    hipLaunchKernelGGL(k_grid_scan_write_b, sgrid, dim3(kGridScanBlock), 0, bs, J);
-    hipLaunchKernelGGL(k_grid_claim_b, pgrid, blk, 0, bs, J);
-    hipLaunchKernelGGL(k_grid_place_b, pgrid, blk, 0, bs, J);
+    grid_emit(R, kGridBin | kGridOrder);
     LO_HIP(e, hipGetLastError());
     return rc;
 }
-}  // namespace
 
-int batch_grids_from_device(lo_batch* b, const GridSrc* src, int n, std::string* err, int* bad_job) {
-    GridErr e;
-    int bad = -1;
-    const int rc = bg_run(b, src, n, &e, &bad);
-    if (err) *err = e.err;
-    if (bad_job) *bad_job = bad;
-    return rc;
-}
-
-}  // namespace lo
-
-extern "C" {
-
-int lo_map_set_points(lo_ctx* c, const float* xyz, size_t m) {
-    if (!c) return LO_ERR_ARG;
-    { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
-    if (!c->kd) { c->err = "lo_map_set_points needs use_surfel_correspondence = 0"; return LO_ERR_STATE; }
-    c->grid_dev = false;
-    return grid_build(c, c->grid, xyz, m);
-}
-
-}  // extern "C"
-
-namespace lo {
 // The kd visit order for a grid whose points are on the device only (grid_from_device, all_pairs_device): its points
 // back in index order (each grid point carries its index), then the host build with the order -- the same grid plus
 // the order.
@@ -696,6 +629,14 @@ int grid_add_order(lo_ctx* c) {
 }  // namespace lo
 
 extern "C" {
+
+int lo_map_set_points(lo_ctx* c, const float* xyz, size_t m) {
+    if (!c) return LO_ERR_ARG;
+    { const int rcf = flush_hold(c); if (rcf != LO_OK) return rcf; }
+    if (!c->kd) { c->err = "lo_map_set_points needs use_surfel_correspondence = 0"; return LO_ERR_STATE; }
+    c->grid_dev = false;
+    return grid_build(c, c->grid, xyz, m);
+}
 
 int lo_kd_reruns(const lo_ctx* c) { return c ? c->kd_reruns : -1; }
 long long lo_loop_reruns(const lo_ctx* c) { return c ? static_cast<long long>(c->loop_reruns) : -1; }

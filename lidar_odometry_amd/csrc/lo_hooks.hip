@@ -489,13 +489,10 @@ int lo_debug_counters(lo_ctx* c, unsigned long long out[16]) {
     return LO_OK;
 }
 
-int lo_debug_grid(lo_ctx* c, float* h, int org[3], int dim[3], int* m, uint32_t* start, size_t start_cap, float* pts4,
-                  size_t pts_cap) {
-    if (!c) return LO_ERR_ARG;
-    if (!c->kd) { c->err = "lo_debug_grid needs use_surfel_correspondence = 0"; return LO_ERR_STATE; }
+static int debug_grid(lo_ctx* c, const PointGrid& G, float* h, int org[3], int dim[3], int* m, uint32_t* start,
+                      size_t start_cap, float* pts4, size_t pts_cap) {
     LO_HIP(c, sync_all(c));
     LO_HIP(c, hipDeviceSynchronize());                   // a batch stream may have built the grid
-    const PointGrid& G = c->grid;
     if (h) *h = G.h;
     for (int a = 0; a < 3; ++a) {
         if (org) org[a] = G.org[a];
@@ -514,6 +511,17 @@ int lo_debug_grid(lo_ctx* c, float* h, int org[3], int dim[3], int* m, uint32_t*
         LO_HIP(c, hipMemcpy(pts4, G.d_pts, np * sizeof(float4), hipMemcpyDeviceToHost));
     }
     return LO_OK;
+}
+int lo_debug_grid(lo_ctx* c, float* h, int org[3], int dim[3], int* m, uint32_t* start, size_t start_cap, float* pts4,
+                  size_t pts_cap) {
+    if (!c) return LO_ERR_ARG;
+    if (!c->kd) { c->err = "lo_debug_grid needs use_surfel_correspondence = 0"; return LO_ERR_STATE; }
+    return debug_grid(c, c->grid, h, org, dim, m, start, start_cap, pts4, pts_cap);
+}
+int lo_debug_loop_grid(lo_ctx* c, float* h, int org[3], int dim[3], int* m, uint32_t* start, size_t start_cap,
+                       float* pts4, size_t pts_cap) {
+    if (!c) return LO_ERR_ARG;
+    return debug_grid(c, c->lgrid, h, org, dim, m, start, start_cap, pts4, pts_cap);
 }
 
 int lo_debug_counters_ex(lo_ctx* c, unsigned long long* out, int n) {

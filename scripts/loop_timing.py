@@ -50,4 +50,27 @@ h, d = np.asarray(host_ms), np.asarray(dev_ms)
 print(f"per call over {len(pairs)} pairs, {ROUNDS} rounds after {WARM} warm-up: host entry median {np.median(h):.3f} ms "
       f"(min {h.min():.3f}, max {h.max():.3f}); device entry median {np.median(d):.3f} ms "
       f"(min {d.min():.3f}, max {d.max():.3f}); ratio {np.median(h) / np.median(d):.3f}")
+
+# ---- the grid path: a matched cloud beyond kKnnAllMax (the 11.6k points of tests/test_gpu_loop_dev.py::
+# test_grid_path_equals_host_entry), whose cell grid the device entry builds on the device with the occupancy rule
+import oracle  # noqa: E402
+
+cur, Tc, _, Tm, _ = _data.loop_case(4, 7, 3)
+mat = oracle.voxel_filter(_data.kitti_scan(4, 40), 0.3, 1)
+dcur, dmat = torch.from_numpy(cur).cuda(), torch.from_numpy(mat).cuda()
+torch.cuda.synchronize()
+host_ms, dev_ms = [], []
+for rnd in range(WARM + ROUNDS):
+    t0 = time.perf_counter()
+    icp.optimize_loop(cur, Tc, mat, Tm)
+    t1 = time.perf_counter()
+    icp.optimize_loop_dev(dcur, Tc, dmat, Tm)
+    t2 = time.perf_counter()
+    if rnd >= WARM:
+        host_ms.append(1e3 * (t1 - t0))
+        dev_ms.append(1e3 * (t2 - t1))
+h, d = np.asarray(host_ms), np.asarray(dev_ms)
+print(f"grid path, {len(mat)} matched points, {ROUNDS} rounds after {WARM} warm-up: host entry median {np.median(h):.3f} ms "
+      f"(min {h.min():.3f}, max {h.max():.3f}); device entry median {np.median(d):.3f} ms "
+      f"(min {d.min():.3f}, max {d.max():.3f})")
 icp.close()
