@@ -377,6 +377,50 @@ double lo_batch_filter_ms(const lo_batch* b);
  * IterativeClosestPointOptimizer::optimize, per sequence.  Errors as lo_batch_filter_raw. */
 int lo_batch_optimize_raw(lo_batch* b, const float* const* raw, const size_t* n_raw, int stride, float voxel_size,
                           const float* T_init, lo_batch_rec* out, size_t* n_filtered);
+/* Batched loop-closure ICP: lo_icp_optimize_loop_dev (below) for many jobs in one lockstep run -- K loop candidates of
+ * a batch's sequences verified by one call.  jobs[i] names a context of the batch (each at most once per call) and
+ * carries what lo_icp_optimize_loop_dev takes for it; out[i] is that entry's result on context `job` with the same
+ * inputs and the same arithmetic mode (each context keeps its own, a call may mix them): status, converged,
+ * iterations, n_corr, T_rel, inlier_ratio, the costs and the iteration logs are bit-identical.  Works on a surfel or a
+ * KDTree batch: every job uses its context's separate loop grid, the contexts' odometry maps and grids are untouched.
+ * All jobs' matched clouds go to the world in one launch; the cell grids of the jobs with n_matched > 8192 are built
+ * by the batch grid builder in one set of launches per tried cell edge (at most four readbacks whatever the job
+ * count); then every Gauss-Newton iteration is one launch per kernel for all jobs (the all-pairs search from LDS, or
+ * the grid search and its unresolved pass for the cell-grid jobs; the plane fit; lo_batch_optimize_async's PKO /
+ * accumulate / solve forms), up to 100 iterations in chunks of 4; after each chunk one small kernel gathers every
+ * job's state into one pinned array and ONE copy and ONE synchronise cover the whole batch, so the host cost per chunk
+ * does not grow with the job count; the inlier pass runs for the converged jobs only.  Synchronous.
+ * A reference-exact job with n_curr > 8192 runs through lo_icp_optimize_loop_dev on its own context inside the call
+ * instead, one after another (the sequential-sum reproductions of larger clouds have no lockstep form, as in
+ * lo_batch_optimize_async).  A lockstep job that met a deciding distance tie is run again alone on its
+ * context with the kd visit order, as the solo entry does: its record is that run's, rerun = 1, and the context's
+ * lo_loop_reruns counts it.  A job with n_curr = 0 or n_matched = 0 reports LO_INSUFFICIENT with 0 iterations and its
+ * context gets no launches.  count = 0: LO_OK, nothing enqueued.
+ * logs (nullable): count x LO_MAX_ITERS entries, job i's at logs + i * LO_MAX_ITERS.  gpu_ms (nullable): device time
+ * of the lockstep part (HIP events on the batch stream).
+ * Errors (text in lo_batch_last_error, naming the job; nothing is enqueued): LO_ERR_ARG for a null array with
+ * count > 0, a job index out of range, a job listed twice or a null cloud pointer with a non-zero count;
+ * LO_ERR_CAPACITY for n_curr > the context's max_points; LO_ERR_STATE while a batch is in flight.  A non-finite
+ * matched world point is LO_ERR_ARG for the call, found after the world transform and before any GN launch. */
+typedef struct lo_loop_job {
+    int          job;            /* index into the batch's contexts; each at most once per call */
+    const float* d_curr;         /* device, AoS float3; may be context job's own scan buffer (used in place) */
+    size_t       n_curr;
+    float        T_curr[12];
+    const float* d_matched;      /* device, AoS float3, e.g. lo_gmap_keyframe_points */
+    size_t       n_matched;
+    float        T_matched[12];
+} lo_loop_job;
+typedef struct lo_loop_rec {
+    int   status;                /* LO_OK / LO_INSUFFICIENT: lo_icp_optimize_loop_dev's return for this job */
+    int   converged, iterations, n_corr;
+    float T_rel[12];             /* written only when converged, as the solo entry; else left as the caller set it */
+    float inlier_ratio;          /* likewise */
+    float initial_cost, final_cost;
+    int   rerun;                 /* 1: the job met a deciding distance tie and was run again with the kd visit order */
+} lo_loop_rec;
+int lo_batch_optimize_loop_dev(lo_batch* b, const lo_loop_job* jobs, int count, lo_loop_rec* out,
+                               lo_iter_log* logs /* nullable: count x LO_MAX_ITERS */, double* gpu_ms /* nullable */);
 
 /* ---- single-stage entry points (parity harness; each synchronous) ---- */
 /* ---- device preprocessing + optimize (Estimator::preprocess_frame, Estimator.cpp:561-588) ----

@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = (
     "lo_batch_create", "lo_batch_destroy", "lo_batch_last_error", "lo_batch_size", "lo_batch_optimize_async",
     "lo_batch_result", "lo_batch_optimize", "lo_batch_bench_correspond",
     "lo_batch_filter_raw", "lo_batch_filter_raw_host", "lo_batch_filter_ms", "lo_batch_optimize_raw",
+    "lo_batch_optimize_loop_dev",
     # include/lo_map.h
     "lo_voxelmap_create", "lo_voxelmap_destroy", "lo_voxelmap_update", "lo_voxelmap_l0_count",
     "lo_voxelmap_l1_count", "lo_voxelmap_surfel_count", "lo_voxelmap_get_surfels", "lo_voxelmap_get_l0", "lo_voxelmap_changed_l1", "lo_voxelmap_surfel_at", "lo_voxelmap_surfels_at_keys",
@@ -96,6 +97,17 @@ class LoStats(C.Structure):
 class LoBatchRec(C.Structure):
     _fields_ = [("pose", C.c_float * 12), ("status", C.c_int), ("iterations", C.c_int), ("n_corr", C.c_int),
                 ("initial_cost", C.c_float), ("final_cost", C.c_float), ("pad", C.c_float), ("alpha", C.c_double)]
+
+
+class LoLoopJob(C.Structure):
+    _fields_ = [("job", C.c_int), ("d_curr", C.c_void_p), ("n_curr", C.c_size_t), ("T_curr", C.c_float * 12),
+                ("d_matched", C.c_void_p), ("n_matched", C.c_size_t), ("T_matched", C.c_float * 12)]
+
+
+class LoLoopRec(C.Structure):
+    _fields_ = [("status", C.c_int), ("converged", C.c_int), ("iterations", C.c_int), ("n_corr", C.c_int),
+                ("T_rel", C.c_float * 12), ("inlier_ratio", C.c_float), ("initial_cost", C.c_float),
+                ("final_cost", C.c_float), ("rerun", C.c_int)]
 
 
 class LoOdomConfig(C.Structure):
@@ -326,6 +338,9 @@ def lib():
     L.lo_batch_filter_ms.argtypes = [vp]
     L.lo_batch_optimize_raw.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_int, C.c_float, fp,
                                         C.POINTER(LoBatchRec), C.POINTER(C.c_size_t)]
+    L.lo_batch_optimize_loop_dev.restype = C.c_int
+    L.lo_batch_optimize_loop_dev.argtypes = [vp, C.POINTER(LoLoopJob), C.c_int, C.POINTER(LoLoopRec),
+                                             C.POINTER(LoIterLog), dp]
     L.lo_batch_update_maps.argtypes = [vp, C.POINTER(vp), u8p, fp, C.c_double]
     L.lo_batch_maps_status.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int)]
     L.lo_batch_sync_points.argtypes = [vp, C.POINTER(vp), u8p]

@@ -88,6 +88,9 @@ struct lo_batch {
     // lo_batch_sync_points (lo_grid.hip): the same for the batched grid build
     void* grid_state = nullptr;
     void (*grid_state_release)(void*) = nullptr;
+    // lo_batch_optimize_loop_dev (lo_batch_loop.hip): the same for the batched loop-closure ICP
+    void* loop_state = nullptr;
+    void (*loop_state_release)(void*) = nullptr;
 };
 
 namespace lo {
@@ -103,6 +106,10 @@ void** batch_map_state(lo_batch* b, void (*release)(void*)) {
 void** batch_grid_state(lo_batch* b, void (*release)(void*)) {
     b->grid_state_release = release;
     return &b->grid_state;
+}
+void** batch_loop_state(lo_batch* b, void (*release)(void*)) {
+    b->loop_state_release = release;
+    return &b->loop_state;
 }
 }  // namespace lo
 
@@ -265,6 +272,7 @@ void lo_batch_destroy(lo_batch* b) {
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     if (b->map_state && b->map_state_release) b->map_state_release(b->map_state);
     if (b->grid_state && b->grid_state_release) b->grid_state_release(b->grid_state);
+    if (b->loop_state && b->loop_state_release) b->loop_state_release(b->loop_state);
     if (b->ev0) (void)hipEventDestroy(b->ev0);
     if (b->ev1) (void)hipEventDestroy(b->ev1);
     if (b->ev_go) (void)hipEventDestroy(b->ev_go);

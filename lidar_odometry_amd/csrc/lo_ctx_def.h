@@ -190,6 +190,9 @@ void launch_correspond(lo_ctx* c, const KParams& P, int with_stats, bool kd);
 void launch_correspond_first(lo_ctx* c, const KParams& P0, bool kd, int with_stats = 1);
 void launch_exact_scale_any(lo_ctx* c, const KParams& P, int n2, hipStream_t s);
 int enqueue_optimize(lo_ctx* c, const float* d_pts, size_t n, const float T_init[12], const int* n_dev = nullptr);
+int loop_rerun_with_order(lo_ctx* c, const float* d_curr, size_t n_curr, const float T_curr[12], size_t n_matched,
+                          const float T_matched[12], float T_rel_out[12], float* inlier_ratio, lo_iter_log* logs,
+                          lo_stats* st);
 // lo_scanq.hip
 inline ScanLane& cur(lo_ctx* c) { return c->q.lanes[c->q.lane]; }   // the lane of the last enqueued scan
 int lane_alloc_base(lo_ctx* c, ScanLane& L);    // everything but the candidate buffers, sized by max_points

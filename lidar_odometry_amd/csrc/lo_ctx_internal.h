@@ -63,6 +63,8 @@ void batch_set_error(lo_batch* b, const char* msg);
 void** batch_map_state(lo_batch* b, void (*release)(void*));
 // the same kind of slot for the batched grid build (lo_grid.hip: batch_grids_from_device)
 void** batch_grid_state(lo_batch* b, void (*release)(void*));
+// and for the batched loop-closure ICP (lo_batch_loop.hip: lo_batch_optimize_loop_dev)
+void** batch_loop_state(lo_batch* b, void (*release)(void*));
 
 // ctx_grid_from_device for the jobs of a KDTree batch in one set of launches on the batch stream (lo_batch_sync_points,
 // lo_map.h): src[a] is active job `job`'s point array on its context `c`.  One readback (bounds and raw count of every
@@ -77,4 +79,18 @@ struct GridSrc {
     int job;
 };
 int batch_grids_from_device(lo_batch* b, const GridSrc* src, int n, std::string* err, int* bad_job);
+// The loop-closure ICP's cell grids for the jobs of a batched call (lo_batch_optimize_loop_dev), each into its context's
+// loop grid under the loop path's occupancy rule (min_per_cell, grid_widen), no visit order: what loop_map_from_device
+// builds per context, in one set of launches per tried cell edge on the batch stream.  xyz: the job's matched cloud in
+// the world (float3, m points), count / occ: device words holding m and receiving the occupied-cell count.
+struct LoopGridSrc {
+    lo_ctx* c;
+    const float* xyz;
+    const int* count;
+    uint32_t* occ;
+    size_t m;
+    int job;
+};
+int batch_loop_grids_from_device(lo_batch* b, const LoopGridSrc* src, int n, int min_per_cell, const uint32_t* h_bad,
+                                 int n_bad, int* bad_slot, std::string* err);
 }  // namespace lo

@@ -604,6 +604,126 @@ int batch_grids_from_device(lo_batch* b, const GridSrc* src, int n, std::string*
     return rc;
 }
 
+// ---- the loop grids of a batch (lo_batch_optimize_loop_dev): loop_map_from_device's grid build for all cell-grid jobs
+// of a call, on the batch stream with the batch's descriptors and the same kernels.  Each job's world cloud (float3,
+// its count in a device word) goes into its context's lgrid under the loop path's occupancy rule: every round bins the
+// jobs that are still asking at their current cell edge (clear + keys, the occupied cells counted), one readback of
+// the counts and one synchronise for all of them, and grid_widen decides per job -- at most four rounds whatever the
+// number of jobs.  Then the order phases once, over every job at its final geometry.  No visit order is built.
+// h_bad (nullable): n_bad host words the caller's copy on the batch stream fills before the bounds readback; a
+// non-zero word ends the call with LO_ERR_ARG (*bad_slot: its index) before any grid is touched.
+int batch_loop_grids_from_device(lo_batch* b, const LoopGridSrc* src, int n, int min_per_cell, const uint32_t* h_bad,
+                                 int n_bad, int* bad_slot, std::string* err) {
+    struct Err { std::string err, *out; ~Err() { if (out) *out = err; } } err_{{}, err}, *e = &err_;   // LO_HIP's handle
+    if (bad_slot) *bad_slot = -1;
+    const BatchView V = batch_view(b);
+    LO_HIP(e, hipSetDevice(V.device));
+    void** slot = batch_grid_state(b, bg_release);
+    if (!*slot) {
+        BatchGrids* S = new BatchGrids();
+        S->device = V.device;
+        *slot = S;                                           // owned by the batch from here on
+    }
+    BatchGrids* S = static_cast<BatchGrids*>(*slot);
+    const size_t B = static_cast<size_t>(std::max(V.count, n));
+    if (!S->ev_up) LO_HIP(e, hipEventCreateWithFlags(&S->ev_up, hipEventDisableTiming));
+    LO_HIP(e, S->d_jobs.reserve(B));
+    LO_HIP(e, S->h_jobs.reserve(B));
+    LO_HIP(e, S->d_bounds.reserve(7 * B));
+    LO_HIP(e, S->h_bounds.reserve(8 * B));                   // the bounds, then the open jobs' occupied-cell words
+    hipStream_t bs = static_cast<hipStream_t>(V.stream);
+    auto upload = [&](int k) -> hipError_t {                 // h_jobs[0 .. k) to the device; ev_up: the copy has read them
+        hipError_t r = hipMemcpyAsync(S->d_jobs, S->h_jobs, sizeof(GridJob) * k, hipMemcpyHostToDevice, bs);
+        if (r == hipSuccess) r = hipEventRecord(S->ev_up, bs);
+        S->up_pending = r == hipSuccess;
+        return r;
+    };
+    auto settle = [&]() -> hipError_t {                      // h_jobs may be rewritten
+        if (!S->up_pending) return hipSuccess;
+        S->up_pending = false;
+        return hipEventSynchronize(S->ev_up);
+    };
+    LO_HIP(e, settle());
+    std::vector<GridJob> fin(static_cast<size_t>(std::max(n, 0)));
+    for (int a = 0; a < n; ++a) S->h_jobs[a] = fin[a] = grid_job_of(src[a].xyz, src[a].count, src[a].m);
+    if (n > 0) {
+        LO_HIP(e, upload(n));
+        hipLaunchKernelGGL(k_grid_bounds_b, dim3(1, n), dim3(1024), 0, bs, S->d_jobs.get(), S->d_bounds.get());
+        LO_HIP(e, hipGetLastError());
+        LO_HIP(e, hipMemcpyAsync(S->h_bounds, S->d_bounds, sizeof(float) * 7 * n, hipMemcpyDeviceToHost, bs));
+    }
+    LO_HIP(e, hipStreamSynchronize(bs));
+    for (int a = 0; a < n_bad; ++a)
+        if (h_bad && h_bad[a]) {
+            if (bad_slot) *bad_slot = a;
+            e->err = "non-finite map point";
+            return LO_ERR_ARG;
+        }
+    if (n <= 0) return LO_OK;
+    std::vector<GridGeom> g(static_cast<size_t>(n));
+    std::vector<char> open(static_cast<size_t>(n), 1);
+    for (int a = 0; a < n; ++a) {
+        g[a] = GridGeom{2.0f * src[a].c->cfg.voxel_size, {0, 0, 0}, {1, 1, 1}};
+        if (grid_count(S->h_bounds + 7 * a) != src[a].m) {
+            e->err = "job " + std::to_string(src[a].job) + ": loop grid: the device count is not the job's";
+            return LO_ERR_STATE;
+        }
+    }
+    uint32_t* h_occ = reinterpret_cast<uint32_t*>(S->h_bounds.get());    // (behind the 7 n bounds)
+    std::vector<int> act;
+    for (int grow = 0;; ++grow) {
+        act.clear();
+        for (int a = 0; a < n; ++a) if (open[a]) act.push_back(a);
+        if (act.empty()) break;
+        LO_HIP(e, settle());
+        size_t max_n = 1, max_m = 1;
+        bool any_rule = false;
+        int k = 0;
+        for (int a : act) {
+            const size_t m = src[a].m;
+            const size_t ncell = grid_fit(S->h_bounds + 7 * a, m, g[a].h, g[a].org, g[a].dim);
+            LO_HIP(e, grid_job_bind(fin[a], src[a].c->lgrid, src[a].c->gscr, m, ncell, g[a]));
+            const bool rule = grid_widen(min_per_cell, grow, m, m);
+            fin[a].occ = rule ? src[a].occ : nullptr;
+            if (rule) LO_HIP(e, hipMemsetAsync(src[a].occ, 0, sizeof(uint32_t), bs));
+            any_rule = any_rule || rule;
+            S->h_jobs[k++] = fin[a];
+            max_n = std::max(max_n, ncell + 1);
+            max_m = std::max(max_m, m);
+        }
+        LO_HIP(e, upload(k));
+        grid_emit(grid_run(bs, S->d_jobs, nullptr, k, max_m, max_n), kGridBin);
+        LO_HIP(e, hipGetLastError());
+        if (!any_rule) break;                                // nobody can ask: every open job is at its final edge
+        // the open jobs' occupied-cell words sit side by side (src[].occ = base + slot): one copy of the span
+        const uint32_t* lo_occ = src[act.front()].occ;
+        const uint32_t* hi_occ = lo_occ;
+        for (int a : act) { lo_occ = std::min(lo_occ, static_cast<const uint32_t*>(src[a].occ)); hi_occ = std::max(hi_occ, static_cast<const uint32_t*>(src[a].occ)); }
+        const size_t span = static_cast<size_t>(hi_occ - lo_occ) + 1;
+        if (7 * static_cast<size_t>(n) + span > S->h_bounds.capacity()) { e->err = "loop grid: occupancy words out of range"; return LO_ERR_STATE; }
+        LO_HIP(e, hipMemcpyAsync(h_occ + 7 * n, lo_occ, sizeof(uint32_t) * span, hipMemcpyDeviceToHost, bs));
+        LO_HIP(e, hipStreamSynchronize(bs));
+        for (int a : act) {
+            const uint32_t occupied = h_occ[7 * n + (static_cast<const uint32_t*>(src[a].occ) - lo_occ)];
+            if (fin[a].occ && grid_widen(min_per_cell, grow, src[a].m, occupied)) g[a].h *= 2.0f;
+            else open[a] = 0;
+        }
+    }
+    size_t max_n = 1, max_m = 1;
+    for (int a = 0; a < n; ++a) { max_n = std::max<size_t>(max_n, fin[a].n); max_m = std::max(max_m, src[a].m); }
+    const GridRun R = grid_run(bs, S->d_jobs, nullptr, n, max_m, max_n);
+    LO_HIP(e, S->d_bsum.reserve(std::max(static_cast<size_t>(kGridBatchWGs), B)));      // >= nblk * n
+    LO_HIP(e, settle());
+    for (int a = 0; a < n; ++a) {
+        grid_job_scan(fin[a], R.nblk, S->d_bsum + static_cast<size_t>(a) * R.nblk);
+        S->h_jobs[a] = fin[a];
+    }
+    LO_HIP(e, upload(n));
+    grid_emit(R, kGridOrder);
+    LO_HIP(e, hipGetLastError());
+    return LO_OK;
+}
+
 // The kd visit order for a grid whose points are on the device only (grid_from_device, all_pairs_device): its points
 // back in index order (each grid point carries its index), then the host build with the order -- the same grid plus
 // the order.

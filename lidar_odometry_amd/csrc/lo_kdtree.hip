@@ -585,8 +585,8 @@ __device__ __forceinline__ float wave_min(float f) {
 // seed (GN iterations after the first): the query's five neighbours of the previous iteration are five points of the
 // set, so the largest of their distances at the new pose bounds the fifth distance from above -- thr starts there and
 // only the few points within it reach the insert (without a seed, thr is the wave's smallest fifth distance so far).
-__device__ __forceinline__ void knn_all_body(const KParams& P, const float (&T)[12], const float4* s_map, bool seed) {
-    const int i = blockIdx.x * (kAllThreads / kWave) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+__device__ __forceinline__ void knn_all_body(const KParams& P, const float (&T)[12], const float4* s_map, bool seed, int blk) {
+    const int i = blk * (kAllThreads / kWave) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (i >= scan_n(P)) return;                              // whole waves leave together
     int32_t* out = P.kd_nbr + 5 * static_cast<size_t>(i);
     float qx, qy, qz;
@@ -673,7 +673,7 @@ __global__ __launch_bounds__(kAllThreads) void k_knn_all(KParams P) {
     float T[12];
     scan_pose(P, P.init, blockIdx.x, T);
     stage_all(P, s_map);
-    knn_all_body(P, T, s_map, !P.init);
+    knn_all_body(P, T, s_map, !P.init, blockIdx.x);
 }
 
 // k_pick_knn over a small set
@@ -686,14 +686,13 @@ __global__ __launch_bounds__(kAllThreads) void k_pick_knn_all(KParams P, int it)
 #pragma unroll
     for (int k = 0; k < 12; ++k) T[k] = s_rec[k];
     stage_all(P, s_map);
-    knn_all_body(P, T, s_map, true);
+    knn_all_body(P, T, s_map, true, blockIdx.x);
 }
 
 // k_inlier over a small set, a wave per point: its lanes take every 64th point until one lies within 1 m (an existence
 // test, so the order of the scan does not matter).  std::sqrt(sqdist) < 1.0f (:233) is sqdist < 1.0f: a correctly
 // rounded square root is monotone and exact at 1, and the largest float below 1 has its root rounded below 1.
-__global__ __launch_bounds__(kAllThreads) void k_inlier_all(KParams P) {
-    extern __shared__ float4 s_map[];
+__device__ __forceinline__ void inlier_all_body(const KParams& P, float4* s_map, int blk) {
     __shared__ unsigned s_hits[kAllThreads / kWave];
     DevState* st = P.st;
     float T[12];
@@ -701,7 +700,7 @@ __global__ __launch_bounds__(kAllThreads) void k_inlier_all(KParams P) {
     for (int k = 0; k < 12; ++k) T[k] = st->pose[k];
     stage_all(P, s_map);
     const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int i = blockIdx.x * (kAllThreads / kWave) + wid;
+    const int i = blk * (kAllThreads / kWave) + wid;
     bool in = false;
     if (i < scan_n(P)) {
         const float px = P.pts[3 * i], py = P.pts[3 * i + 1], pz = P.pts[3 * i + 2];
@@ -730,6 +729,10 @@ __global__ __launch_bounds__(kAllThreads) void k_inlier_all(KParams P) {
         for (int w = 0; w < kAllThreads / kWave; ++w) h += s_hits[w];
         if (h) atomicAdd(&st->inliers, h);
     }
+}
+__global__ __launch_bounds__(kAllThreads) void k_inlier_all(KParams P) {
+    extern __shared__ float4 s_map[];
+    inlier_all_body(P, s_map, blockIdx.x);
 }
 
 // lo_knn_search (kNN without the plane stage): the unresolved-query counter k_plane would zero
@@ -931,14 +934,39 @@ __global__ __launch_bounds__(kBlock) void k_plane_b(const KParams* __restrict__ 
     plane_body(P, with_stats, blk);
 }
 
+// The batched loop-closure ICP (lo_batch_optimize_loop_dev): k_knn_all and k_inlier_all per job, a wave per query on
+// the grid of the call's largest job (16 queries per workgroup), dynamic LDS sized for the call's largest set.  The
+// early exits are uniform over the workgroup and come before stage_all's barrier: a job's surplus workgroups leave
+// before touching its buffers, a finished job leaves at once.
+__global__ __launch_bounds__(kAllThreads) void k_knn_all_b(const KParams* __restrict__ PB, int init) {
+    extern __shared__ float4 s_map[];
+    int job, blk;
+    batch_block(job, blk);
+    const KParams& P = PB[job];
+    if (!P.kd_all) return;                                   // a cell-grid job of the call: k_knn_b + k_knn_brute_b
+    if (blk * (kAllThreads / kWave) >= P.n) return;
+    if (!init && P.st->done) return;
+    float T[12];
+    scan_pose(P, init, blk, T);
+    stage_all(P, s_map);
+    knn_all_body(P, T, s_map, !init, blk);
+}
+// sel[blockIdx.y]: the converged jobs' slots in PB (the inlier ratio is taken of a converged solve only)
+__global__ __launch_bounds__(kAllThreads) void k_inlier_all_b(const KParams* __restrict__ PB, const int* __restrict__ sel) {
+    extern __shared__ float4 s_map[];
+    const KParams& P = PB[sel[blockIdx.y]];
+    if (static_cast<int>(blockIdx.x) * (kAllThreads / kWave) >= P.n) return;
+    inlier_all_body(P, s_map, blockIdx.x);
+}
+
 // optimize_loop's inlier ratio (:206-238): the curr cloud at the converged pose (t + R p, :220-221), each point an
 // inlier when its nearest matched-map point is closer than 1 m: sqrt of nanoflann's fp32 (dx^2 + dy^2) + dz^2 < 1.
 // Every map point within 1 m lies in the cells spanned by q +- (1 m + kKnnMargin) (the margin covers the fp32
 // rounding of q / h and of the grid's own cell index), so the grid answers the 1-NN threshold test exactly.  One
 // lane per point, a row's points 8 loads at a time, early exit on a hit.
-__global__ __launch_bounds__(kBlock) void k_inlier(KParams P) {
+__device__ __forceinline__ void inlier_body(const KParams& P, int blk) {
     DevState* st = P.st;
-    const int i = blockIdx.x * kBlock + threadIdx.x;
+    const int i = blk * kBlock + threadIdx.x;
     bool in = false;
     if (i < scan_n(P)) {
         float T[12];
@@ -980,6 +1008,13 @@ __global__ __launch_bounds__(kBlock) void k_inlier(KParams P) {
     }
     const uint64_t m = __ballot(in);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(&st->inliers, static_cast<unsigned>(__popcll(m)));
+}
+__global__ __launch_bounds__(kBlock) void k_inlier(KParams P) { inlier_body(P, blockIdx.x); }
+// the batched loop-closure ICP's cell-grid jobs: sel[blockIdx.y] as k_inlier_all_b
+__global__ __launch_bounds__(kBlock) void k_inlier_b(const KParams* __restrict__ PB, const int* __restrict__ sel) {
+    const KParams& P = PB[sel[blockIdx.y]];
+    if (static_cast<int>(blockIdx.x) >= P.nb) return;
+    inlier_body(P, blockIdx.x);
 }
 
 }  // namespace lo

@@ -38,6 +38,9 @@ __global__ void k_correspond_b(const KParams* PB, int with_stats, int init);
 __global__ void k_knn_b(const KParams* PB, int init);
 __global__ void k_knn_brute_b(const KParams* PB, int njobs, int per);
 __global__ void k_plane_b(const KParams* PB, int with_stats);
+__global__ void k_knn_all_b(const KParams* PB, int init);
+__global__ void k_inlier_all_b(const KParams* PB, const int* sel);
+__global__ void k_inlier_b(const KParams* PB, const int* sel);
 template <int NW, bool ONE_WAVE> __global__ void k_pko_tb(const KParams* PB, int it);
 __global__ void k_accumulate_b(const KParams* PB, int it);
 template <bool SOLVE> __global__ void k_accumulate_b1(const KParams* PB, int it);

@@ -439,9 +439,8 @@ static constexpr int kLoopMinPerCell = 4;                // the matched cloud's 
 // the visit order then brings the gridded points down, grid_add_order).
 static int loop_solve(lo_ctx* c, const float* curr, bool curr_dev, size_t n_curr, const float T_curr[12], const float* lmap,
                       size_t n_matched, const float T_matched[12], float T_rel_out[12], float* inlier_ratio,
-                      lo_iter_log* logs, lo_stats* st) {
+                      lo_iter_log* logs, lo_stats* st, bool with_order = false) {
     int rc = LO_OK;
-    bool with_order = false;
     // all_pairs_upload has put a host cloud into c->d_pts already; every other case copies it below
     bool curr_staged = !curr_dev && c->lgrid.all;
 retry:
@@ -678,3 +677,17 @@ long long lo_voxel_filter_gpu(lo_ctx* c, const float* raw, size_t n_raw, float v
 }
 
 }  // extern "C"
+
+namespace lo {
+// The rerun of a loop solve that met a deciding distance tie, for a caller that ran the first pass itself (the batched
+// loop ICP, lo_batch_loop.hip): what loop_solve does from its tie test on -- the rerun counted, the kd visit order
+// built from the gridded points of c->lgrid, the solve again on the context stream.
+int loop_rerun_with_order(lo_ctx* c, const float* d_curr, size_t n_curr, const float T_curr[12], size_t n_matched,
+                          const float T_matched[12], float T_rel_out[12], float* inlier_ratio, lo_iter_log* logs,
+                          lo_stats* st) {
+    ++c->loop_reruns;
+    const int rc = grid_add_order(c, c->lgrid, kLoopMinPerCell);
+    if (rc != LO_OK) return rc;
+    return loop_solve(c, d_curr, true, n_curr, T_curr, nullptr, n_matched, T_matched, T_rel_out, inlier_ratio, logs, st, true);
+}
+}  // namespace lo

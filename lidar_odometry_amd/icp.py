@@ -432,6 +432,22 @@ class BatchResult:
     alpha: float
 
 
+@dataclass
+class LoopBatchResult:
+    """One job of a batched loop-closure ICP: the fields of lo_loop_rec, and the executed iterations' logs as the raw
+    bytes of their lo_iter_log records."""
+    status: int
+    converged: bool
+    iterations: int
+    n_corr: int
+    T_rel: np.ndarray
+    inlier_ratio: np.float32
+    initial_cost: np.float32
+    final_cost: np.float32
+    rerun: bool
+    logs: bytes
+
+
 class BatchOptimizer:
     """Scan-parallel optimize on one GPU (lo_batch_*): B independent contexts -- B sequences, each with its own
     map and GN state -- run IterativeClosestPointOptimizer::optimize in lockstep, one launch per kernel per GN
@@ -557,6 +573,51 @@ class BatchOptimizer:
         self._check(lib().lo_batch_result(self._b, recs, C.byref(ms)))
         self.last_gpu_ms = ms.value
         return self._results(recs)
+
+    def optimize_loop_dev(self, jobs, sentinel: float = 0.0):
+        """lo_batch_optimize_loop_dev: the loop-closure ICP of many jobs in one lockstep run.  ``jobs`` is a list of
+        ``(job, (ptr, n), T_curr, (ptr, n), T_matched)`` -- the batch's context index, then the current and the matched
+        cloud as ``optimize_loop_dev`` takes them (device pointer as int and count, or an (N, 3) float32 device
+        tensor) with their world poses.  Returns one ``LoopBatchResult`` per job, in the order given; each equals
+        ``optimizers[job].optimize_loop_dev`` on the same inputs bit for bit.  ``T_rel`` and ``inlier_ratio`` are
+        written only for a converged job (else they keep ``sentinel``)."""
+        def dev(x):
+            if hasattr(x, "data_ptr"):
+                if not getattr(x, "is_cuda", False) or x.dim() != 2 or x.shape[1] != 3 or str(x.dtype) != "torch.float32":
+                    raise ValueError("device points must be an (N, 3) float32 device tensor")
+                x = x.contiguous()
+                return x, int(x.data_ptr()), int(x.shape[0])
+            ptr, n = x
+            return None, int(ptr) if ptr else None, int(n)
+        K = len(jobs)
+        arr = (_lib.LoLoopJob * max(K, 1))()
+        keep = []
+        for i, (j, curr, Tc, matched, Tm) in enumerate(jobs):
+            kc, pc, nc = dev(curr)
+            km, pm, nm = dev(matched)
+            keep += [kc, km]
+            arr[i].job, arr[i].d_curr, arr[i].n_curr, arr[i].d_matched, arr[i].n_matched = int(j), pc, nc, pm, nm
+            arr[i].T_curr[:] = _as_pose(Tc).tolist()
+            arr[i].T_matched[:] = _as_pose(Tm).tolist()
+        recs = (_lib.LoLoopRec * max(K, 1))()
+        for r in recs:
+            r.T_rel[:] = [sentinel] * 12
+            r.inlier_ratio = sentinel
+        logs = (LoIterLog * (_lib.LO_MAX_ITERS * max(K, 1)))()
+        ms = C.c_double(0.0)
+        self._check(lib().lo_batch_optimize_loop_dev(self._b, arr, K, recs, logs, C.byref(ms)))
+        del keep
+        self.last_gpu_ms = ms.value
+        out = []
+        base, per, one = C.addressof(logs), _lib.LO_MAX_ITERS * C.sizeof(LoIterLog), C.sizeof(LoIterLog)
+        for i in range(K):
+            r = recs[i]
+            n = min(max(r.iterations, 0), _lib.LO_MAX_ITERS)
+            raw = C.string_at(base + i * per, n * one)         # job i's executed iterations only
+            out.append(LoopBatchResult(r.status, bool(r.converged), r.iterations, r.n_corr,
+                                       np.array(r.T_rel[:], np.float32), np.float32(r.inlier_ratio),
+                                       np.float32(r.initial_cost), np.float32(r.final_cost), bool(r.rerun), raw))
+        return out
 
     def _map_handles(self, maps):
         B = len(self.optimizers)
