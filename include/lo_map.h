@@ -135,6 +135,24 @@ size_t      lo_devmap_get_l1(lo_devmap* m, int32_t* keys, uint8_t* has_surfel, f
  * on the host for the batch's previous update.  LO_ERR_STATE while a batch optimize is in flight. */
 int         lo_batch_update_maps(lo_batch* b, lo_devmap* const* maps, const unsigned char* active, const float* T,
                                  double max_distance);
+/* The map correction after accepted loops, for the jobs of a batch: for every job j with active[j] != 0, what
+ * lo_devmap_apply_transform(maps[j], T + 12*j) does -- ApplyTransformAndRehash (VoxelMap.cpp:264-302), then
+ * RecomputeAllSurfels (:304-366) -- for all active jobs together on the batch stream.  T: count x 12, one row-major 3x4
+ * correction per job; the entries of inactive jobs are not read.  Per call, whatever the number of active jobs: the
+ * single call's nine launches (new keys, rebuild, flag, clear, fill, recompute, flag, clear, fill; blockIdx.y = active
+ * job, the rebuild one workgroup per job, all of them side by side), one host-to-device copy of the corrections, a
+ * descriptor upload only for a job whose entry changed, no synchronise.  Job j's map -- L0 order, keys, centroids and
+ * point counts with the merged voxels; L1 order, children, surfels -- and context j's surfel table afterwards equal
+ * the single call's on an identical map, bit for bit.  The contracts are lo_batch_update_maps': enqueues and returns;
+ * the contexts must be idle; LO_ERR_STATE while a batch optimize is in flight; LO_ERR_ARG for a null argument or an
+ * active job's map that was not created on context j; maps of different capacities may share a batch; single and
+ * batched corrections and updates may alternate on one map (wait for the batch stream before the single call:
+ * lo_batch_maps_status does); a replaced table is refilled first.  A job whose correction gives a key beyond +-2^20 or
+ * overflows a capacity sets its own error bits, which lo_batch_maps_status reports for that job only; a job whose map
+ * is empty changes nothing.  No scan is read: a context that has filtered none is fine.  In a KDTree batch the
+ * contexts' grids still hold the old centroids: the caller follows with lo_batch_sync_points on the same `active`;
+ * this call does not. */
+int         lo_batch_apply_transform(lo_batch* b, lo_devmap* const* maps, const unsigned char* active, const float* T);
 /* Error bits of all jobs' maps in one copy (synchronises the batch stream): rc[j] (nullable) = LO_OK or
  * LO_ERR_CAPACITY; returns LO_OK when every job is LO_OK, else LO_ERR_CAPACITY (lo_batch_last_error names the first
  * such job, and each such map's lo_devmap_last_error is set).  maps[j] may be NULL for a job that has no map: it

@@ -176,8 +176,10 @@ int       lo_odom_save_map_ply(lo_odometry* o, const char* path, float voxel_siz
  * (RebuildKdTree, Estimator.cpp:460-462), and equals a solo KDTree lo_odometry in the same fields and in lo_kd_reruns.
  * lo_odom_batch_last_error(NULL) says why the calling thread's last create failed.  No loop closure in this
  * loop yet: the batched detector exists (lo_iris_batch.h: the candidates of any subset of sequences in one set of
- * launches) and so does the batched loop ICP (lo_icp.h: lo_batch_optimize_loop_dev, the candidates' verification in
- * one lockstep run), but neither is wired in here yet -- that also needs per-sequence PGO and map correction.
+ * launches), so does the batched loop ICP (lo_icp.h: lo_batch_optimize_loop_dev, the candidates' verification in
+ * one lockstep run) and so does the batched map correction (lo_map.h: lo_batch_apply_transform, the corrected
+ * sequences' maps moved and rehashed in one set of launches), but none is wired in here yet -- what remains is
+ * per-sequence PGO (host code, lo_pgo.h) and the wiring.
  * info[j].device_ms is the whole batch's optimize; info[j].map_ms the batched update's enqueue (KDTree: and the grid
  * build with its synchronise). */
 typedef struct lo_odom_batch lo_odom_batch;

@@ -41,7 +41,7 @@ EXPORTED_SYMBOLS = (
     "lo_map_set_from_voxelmap", "lo_map_sync_voxelmap", "lo_voxelmap_apply_transform", "lo_map_patch_surfels", "lo_voxel_filter",
     "lo_voxelmap_set_device_fit", "lo_devmap_create", "lo_devmap_destroy", "lo_devmap_last_error", "lo_devmap_update",
     "lo_devmap_update_from_scan", "lo_devmap_apply_transform", "lo_devmap_counts", "lo_devmap_status", "lo_devmap_status_async", "lo_devmap_status_poll", "lo_devmap_sync_points", "lo_kd_reruns", "lo_devmap_get_l0", "lo_devmap_get_l1",
-    "lo_batch_update_maps", "lo_batch_maps_status", "lo_batch_sync_points",
+    "lo_batch_update_maps", "lo_batch_maps_status", "lo_batch_sync_points", "lo_batch_apply_transform",
     # include/lo_odometry.h
     "lo_odom_config_default_kitti", "lo_odom_create", "lo_odom_destroy", "lo_odom_last_error", "lo_odom_set_initial_pose",
     "lo_odom_process", "lo_odom_keyframe_count", "lo_odom_map_surfels", "lo_odom_kd_reruns", "lo_odom_set_exact", "lo_odom_flush",
@@ -344,6 +344,7 @@ def lib():
     L.lo_batch_update_maps.argtypes = [vp, C.POINTER(vp), u8p, fp, C.c_double]
     L.lo_batch_maps_status.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int)]
     L.lo_batch_sync_points.argtypes = [vp, C.POINTER(vp), u8p]
+    L.lo_batch_apply_transform.argtypes = [vp, C.POINTER(vp), u8p, fp]
     L.lo_odom_batch_create.restype = vp
     L.lo_odom_batch_create.argtypes = [C.POINTER(LoOdomConfig), C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_int)]
     L.lo_odom_batch_create_kdtree.restype = vp

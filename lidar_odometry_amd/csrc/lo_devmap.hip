@@ -1078,96 +1078,38 @@ __device__ __forceinline__ void dm_rebuild_fill_body(const DM& M) {
     }
 }
 
-// ---------------------------------------------------------------------------------------------- the update's kernels
-// Every phase above is a __device__ body on `const DM&`; k_dm_X runs it on one map (the descriptor in the kernel
-// arguments), k_dm_X_b on the maps of a batch: blockIdx.y = active slot, its job's descriptor read from the batch's
-// device array.  blockIdx.x / gridDim.x stay "the workgroups of this map" in both forms.
-struct DMJob {
-    DM M;
-    const float* scan;                   // the context's device-filtered scan and its device count
-    const int* scan_n;
-    float* d_in;                         // the map's world-point buffer
-};
-struct DmJobPrm { DmParams P; int job; int pad; };       // per active slot: this update's parameters and its job
-#define DM_JOB const DMJob* __restrict__ jobs, const DmJobPrm* __restrict__ prm
-#define DM_J const DMJob& J = jobs[prm[blockIdx.y].job]; const DM M = J.M
-
-__global__ __launch_bounds__(kPar) void k_dm_world(DM M, const float* in, const int* dn, float* out) { dm_world_body(M, in, dn, out); }
-__global__ __launch_bounds__(kPar) void k_dm_world_b(DM_JOB) { DM_J; dm_world_body(M, J.scan, J.scan_n, J.d_in); }
-__global__ void k_dm_setprm(DM M, DmParams P) { dm_setprm_body(M, P); }
-__global__ void k_dm_setprm_b(DM_JOB) { DM_J; dm_setprm_body(M, prm[blockIdx.y].P); }
-__global__ __launch_bounds__(kPar) void k_dm_prune_mark(DM M, const int* dn) { dm_prune_mark_body(M, dn); }
-__global__ __launch_bounds__(kPar) void k_dm_prune_mark_b(DM_JOB) { DM_J; dm_prune_mark_body(M, M.prm_n); }
-__global__ __launch_bounds__(kPar) void k_dm_prune_compact(DM M, const int* dn) { dm_prune_compact_body(M, dn); }
-__global__ __launch_bounds__(kPar) void k_dm_prune_compact_b(DM_JOB) { DM_J; dm_prune_compact_body(M, M.prm_n); }
-__global__ __launch_bounds__(kOrch) void k_dm_unregister(DM M) { dm_unregister_body(M); }
-__global__ __launch_bounds__(kOrch) void k_dm_unregister_b(DM_JOB) { DM_J; dm_unregister_body(M); }
-__global__ __launch_bounds__(kPar) void k_dm_keys(DM M, const float* pts, int n_host, const int* dn) { dm_keys_body(M, pts, n_host, dn); }
-__global__ __launch_bounds__(kPar) void k_dm_keys_b(DM_JOB) { DM_J; dm_keys_body(M, J.d_in, 0, M.prm_n); }
-__global__ __launch_bounds__(kPar) void k_dm_a_count(DM M, int n_host, const int* dn) { dm_a_count_body(M, n_host, dn); }
-__global__ __launch_bounds__(kPar) void k_dm_a_count_b(DM_JOB) { DM_J; dm_a_count_body(M, 0, M.prm_n); }
-__global__ __launch_bounds__(kOrch) void k_dm_scan3(DM M, int stage) { dm_scan3_body(M, stage); }
-__global__ __launch_bounds__(kOrch) void k_dm_scan3_b(DM_JOB, int stage) { DM_J; dm_scan3_body(M, stage); }
-__global__ __launch_bounds__(kPar) void k_dm_a_rank(DM M, int n_host, const int* dn) { dm_a_rank_body(M, n_host, dn); }
-__global__ __launch_bounds__(kPar) void k_dm_a_rank_b(DM_JOB) { DM_J; dm_a_rank_body(M, 0, M.prm_n); }
-__global__ __launch_bounds__(kPar) void k_dm_a_fill(DM M, int n_host, const int* dn) { dm_a_fill_body(M, n_host, dn); }
-__global__ __launch_bounds__(kPar) void k_dm_a_fill_b(DM_JOB) { DM_J; dm_a_fill_body(M, 0, M.prm_n); }
-__global__ __launch_bounds__(kPar) void k_dm_a_mean(DM M, const float* pts, int n_host, const int* dn) { dm_a_mean_body(M, pts, n_host, dn); }
-__global__ __launch_bounds__(kPar) void k_dm_a_mean_b(DM_JOB) { DM_J; dm_a_mean_body(M, J.d_in, 0, M.prm_n); }
-__global__ __launch_bounds__(kPar) void k_dm_r_group(DM M) { dm_r_group_body(M); }
-__global__ __launch_bounds__(kPar) void k_dm_r_group_b(DM_JOB) { DM_J; dm_r_group_body(M); }
-__global__ __launch_bounds__(kPar) void k_dm_r_count(DM M) { dm_r_count_body(M); }
-__global__ __launch_bounds__(kPar) void k_dm_r_count_b(DM_JOB) { DM_J; dm_r_count_body(M); }
-__global__ __launch_bounds__(kPar) void k_dm_r_rank(DM M) { dm_r_rank_body(M); }
-__global__ __launch_bounds__(kPar) void k_dm_r_rank_b(DM_JOB) { DM_J; dm_r_rank_body(M); }
-__global__ __launch_bounds__(kPar) void k_dm_r_fill(DM M) { dm_r_fill_body(M); }
-__global__ __launch_bounds__(kPar) void k_dm_r_fill_b(DM_JOB) { DM_J; dm_r_fill_body(M); }
-__global__ __launch_bounds__(kPar) void k_dm_r_append(DM M) { dm_r_append_body(M); }
-__global__ __launch_bounds__(kPar) void k_dm_r_append_b(DM_JOB) { DM_J; dm_r_append_body(M); }
-__global__ __launch_bounds__(kPar) void k_dm_a_done(DM M, int n_host, const int* dn) { dm_a_done_body(M, n_host, dn); }
-__global__ __launch_bounds__(kPar) void k_dm_a_done_b(DM_JOB) { DM_J; dm_a_done_body(M, 0, M.prm_n); }
-__global__ __launch_bounds__(64) void k_dm_touched(DM M) { dm_touched_body(M); }
-__global__ __launch_bounds__(64) void k_dm_touched_b(DM_JOB) { DM_J; dm_touched_body(M); }
-__global__ __launch_bounds__(kOrch) void k_dm_finish(DM M) { dm_finish_body(M); }
-__global__ __launch_bounds__(kOrch) void k_dm_finish_b(DM_JOB) { DM_J; dm_finish_body(M); }
-__global__ __launch_bounds__(kPar) void k_dm_table(DM M) { dm_table_body(M); }
-__global__ __launch_bounds__(kPar) void k_dm_table_b(DM_JOB) { DM_J; dm_table_body(M); }
-__global__ void k_dm_table_check(DM M) { dm_table_check_body(M); }
-__global__ void k_dm_table_check_b(DM_JOB) { DM_J; dm_table_check_body(M); }
-__global__ __launch_bounds__(kPar) void k_dm_rebuild_clear(DM M) { dm_rebuild_clear_body(M); }
-__global__ __launch_bounds__(kPar) void k_dm_rebuild_clear_b(DM_JOB) { DM_J; dm_rebuild_clear_body(M); }
-__global__ __launch_bounds__(kPar) void k_dm_rebuild_fill(DM M) { dm_rebuild_fill_body(M); }
-__global__ __launch_bounds__(kPar) void k_dm_rebuild_fill_b(DM_JOB) { DM_J; dm_rebuild_fill_body(M); }
-// the error bits of all maps of a batch, gathered for one copy (lo_batch_maps_status)
-__global__ __launch_bounds__(kPar) void k_dm_status_b(const DMJob* __restrict__ jobs, int count, int* __restrict__ out) {
-    const int j = blockIdx.x * kPar + threadIdx.x;
-    if (j < count) out[j] = jobs[j].M.cnt ? jobs[j].M.cnt[C_ERR] : 0;      // (a job without a map: cleared entry)
-}
-#undef DM_J
-#undef DM_JOB
-
 // ---------------------------------------------------------------------------------------------- ApplyTransformAndRehash
 // (:264-302) every L0 centroid moved (R c + t, Matrix3f * Vector3f) and re-keyed; the rebuilt L0 holds the keys in
 // first-occurrence order, colliding voxels merged in the old order ((c1 n1 + c2 n2) / (n1 + n2)); every entry
 // registers with its parent, so L1 is ordered by first child and each children set by L0 position.
-__global__ __launch_bounds__(kPar) void k_dm_at_keys(DM M, DmPose T, float* tc, uint64_t* tk) {
-    const int i = blockIdx.x * kPar + threadIdx.x;
-    if (i >= M.cnt[C_N0]) return;
-    const float* c = M.c0 + 3 * i;
-    float o[3];
-    for (int r = 0; r < 3; ++r)
-        o[r] = dot3e(T.v[4 * r], T.v[4 * r + 1], T.v[4 * r + 2], c[0], c[1], c[2]) + T.v[4 * r + 3];
-    float f[3];
-    bool ok = true;
-    for (int a = 0; a < 3; ++a) { tc[3 * i + a] = o[a]; f[a] = floorf(o[a] / M.voxel); ok = ok && key_ok(f[a]); }
-    if (!ok) { atomicOr(&M.cnt[C_ERR], E_KEY); f[0] = f[1] = f[2] = 0.0f; }
-    tk[i] = pack_key(static_cast<int>(f[0]), static_cast<int>(f[1]), static_cast<int>(f[2]));
+// T: the 3x4 correction, row-major.  A grid-stride loop: the grid need not cover the capacity.
+__device__ __forceinline__ void dm_at_keys_body(const DM& M, const float* T, float* tc, uint64_t* tk) {
+    const int n = M.cnt[C_N0];
+    for (int i = blockIdx.x * kPar + threadIdx.x; i < n; i += gridDim.x * kPar) {
+        const float* c = M.c0 + 3 * i;
+        float o[3];
+        for (int r = 0; r < 3; ++r)
+            o[r] = dot3e(T[4 * r], T[4 * r + 1], T[4 * r + 2], c[0], c[1], c[2]) + T[4 * r + 3];
+        float f[3];
+        bool ok = true;
+        for (int a = 0; a < 3; ++a) { tc[3 * i + a] = o[a]; f[a] = floorf(o[a] / M.voxel); ok = ok && key_ok(f[a]); }
+        if (!ok) { atomicOr(&M.cnt[C_ERR], E_KEY); f[0] = f[1] = f[2] = 0.0f; }
+        tk[i] = pack_key(static_cast<int>(f[0]), static_cast<int>(f[1]), static_cast<int>(f[2]));
+    }
 }
 
-__global__ __launch_bounds__(kOrch) void k_dm_at_rebuild(DM M, const float* tc, const uint64_t* tk, int* tslot,
-                                                         int* tfirst, int* tcnt, int* toff, int* tfill, int* glist,
-                                                         int* order, uint64_t* nk0, float* nc0, int* nn0) {
+// One workgroup of kOrch threads per map.  The grouping scratch is the update's, free between updates: the point
+// hashes' slot / first / count / offset / fill arrays, glist and D.
+__device__ __forceinline__ void dm_at_rebuild_body(const DM& M, const float* tc, const uint64_t* tk, uint64_t* nk0,
+                                                   float* nc0, int* nn0) {
     __shared__ int s_w[64];
+    int* const tslot = M.pslot;
+    int* const tfirst = M.tpfirst;
+    int* const tcnt = M.tpcnt;
+    int* const toff = M.tpoff;
+    int* const tfill = M.tpfill;
+    int* const glist = M.glist;
+    int* const order = M.D;
     const int n = M.cnt[C_N0];
     // grouping by new key (hash of capacity 2^hpl >= 2 C0 reserved in the point hashes' place)
     for (int i = threadIdx.x; i < n; i += kOrch) {
@@ -1281,9 +1223,7 @@ __global__ __launch_bounds__(kOrch) void k_dm_at_rebuild(DM M, const float* tc, 
 }
 
 // RecomputeAllSurfels (:304-366): every L1 voxel refitted; failures only lose the surfel
-__global__ __launch_bounds__(kPar) void k_dm_recompute(DM M) {
-    const int lp = blockIdx.x * kPar + threadIdx.x;
-    if (lp >= M.cnt[C_N1]) return;
+__device__ __forceinline__ void dm_recompute_one(const DM& M, int lp) {
     const int cnt = M.nk[lp];
     if (cnt < 5) { M.has[lp] = 0; return; }
     float cs[3 * kKids];
@@ -1303,10 +1243,97 @@ __global__ __launch_bounds__(kPar) void k_dm_recompute(DM M) {
     M.plan[lp] = planarity;
     M.last[lp] = cnt;
 }
+__device__ __forceinline__ void dm_recompute_body(const DM& M) {
+    const int n = M.cnt[C_N1];
+    for (int lp = blockIdx.x * kPar + threadIdx.x; lp < n; lp += gridDim.x * kPar) dm_recompute_one(M, lp);
+}
 
-__global__ __launch_bounds__(kPar) void k_dm_flag(DM M, int flags) {
+__device__ __forceinline__ void dm_flag_body(const DM& M, int flags) {
     if (blockIdx.x == 0 && threadIdx.x == 0) M.cnt[C_REBUILD] |= flags;
 }
+
+
+// ---------------------------------------------------------------------------------------------- the kernels
+// Every phase above, the update's and the correction's, is a __device__ body on `const DM&`; k_dm_X runs it on one map (the descriptor in the kernel
+// arguments), k_dm_X_b on the maps of a batch: blockIdx.y = active slot, its job's descriptor read from the batch's
+// device array.  blockIdx.x / gridDim.x stay "the workgroups of this map" in both forms.
+struct DMJob {
+    DM M;
+    const float* scan;                   // the context's device-filtered scan and its device count
+    const int* scan_n;
+    float* d_in;                         // the map's world-point buffer
+    float* at_c;                         // the map's ApplyTransformAndRehash scratch (lo_devmap::at_*)
+    uint64_t* at_k;
+    uint64_t* at_nk;
+    float* at_nc;
+    int* at_nn;
+};
+struct DmJobPrm { DmParams P; int job; int pad; };       // per active slot: this update's parameters and its job
+#define DM_JOB const DMJob* __restrict__ jobs, const DmJobPrm* __restrict__ prm
+#define DM_J const DMJob& J = jobs[prm[blockIdx.y].job]; const DM M = J.M
+
+__global__ __launch_bounds__(kPar) void k_dm_world(DM M, const float* in, const int* dn, float* out) { dm_world_body(M, in, dn, out); }
+__global__ __launch_bounds__(kPar) void k_dm_world_b(DM_JOB) { DM_J; dm_world_body(M, J.scan, J.scan_n, J.d_in); }
+__global__ void k_dm_setprm(DM M, DmParams P) { dm_setprm_body(M, P); }
+__global__ void k_dm_setprm_b(DM_JOB) { DM_J; dm_setprm_body(M, prm[blockIdx.y].P); }
+__global__ __launch_bounds__(kPar) void k_dm_prune_mark(DM M, const int* dn) { dm_prune_mark_body(M, dn); }
+__global__ __launch_bounds__(kPar) void k_dm_prune_mark_b(DM_JOB) { DM_J; dm_prune_mark_body(M, M.prm_n); }
+__global__ __launch_bounds__(kPar) void k_dm_prune_compact(DM M, const int* dn) { dm_prune_compact_body(M, dn); }
+__global__ __launch_bounds__(kPar) void k_dm_prune_compact_b(DM_JOB) { DM_J; dm_prune_compact_body(M, M.prm_n); }
+__global__ __launch_bounds__(kOrch) void k_dm_unregister(DM M) { dm_unregister_body(M); }
+__global__ __launch_bounds__(kOrch) void k_dm_unregister_b(DM_JOB) { DM_J; dm_unregister_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_keys(DM M, const float* pts, int n_host, const int* dn) { dm_keys_body(M, pts, n_host, dn); }
+__global__ __launch_bounds__(kPar) void k_dm_keys_b(DM_JOB) { DM_J; dm_keys_body(M, J.d_in, 0, M.prm_n); }
+__global__ __launch_bounds__(kPar) void k_dm_a_count(DM M, int n_host, const int* dn) { dm_a_count_body(M, n_host, dn); }
+__global__ __launch_bounds__(kPar) void k_dm_a_count_b(DM_JOB) { DM_J; dm_a_count_body(M, 0, M.prm_n); }
+__global__ __launch_bounds__(kOrch) void k_dm_scan3(DM M, int stage) { dm_scan3_body(M, stage); }
+__global__ __launch_bounds__(kOrch) void k_dm_scan3_b(DM_JOB, int stage) { DM_J; dm_scan3_body(M, stage); }
+__global__ __launch_bounds__(kPar) void k_dm_a_rank(DM M, int n_host, const int* dn) { dm_a_rank_body(M, n_host, dn); }
+__global__ __launch_bounds__(kPar) void k_dm_a_rank_b(DM_JOB) { DM_J; dm_a_rank_body(M, 0, M.prm_n); }
+__global__ __launch_bounds__(kPar) void k_dm_a_fill(DM M, int n_host, const int* dn) { dm_a_fill_body(M, n_host, dn); }
+__global__ __launch_bounds__(kPar) void k_dm_a_fill_b(DM_JOB) { DM_J; dm_a_fill_body(M, 0, M.prm_n); }
+__global__ __launch_bounds__(kPar) void k_dm_a_mean(DM M, const float* pts, int n_host, const int* dn) { dm_a_mean_body(M, pts, n_host, dn); }
+__global__ __launch_bounds__(kPar) void k_dm_a_mean_b(DM_JOB) { DM_J; dm_a_mean_body(M, J.d_in, 0, M.prm_n); }
+__global__ __launch_bounds__(kPar) void k_dm_r_group(DM M) { dm_r_group_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_r_group_b(DM_JOB) { DM_J; dm_r_group_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_r_count(DM M) { dm_r_count_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_r_count_b(DM_JOB) { DM_J; dm_r_count_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_r_rank(DM M) { dm_r_rank_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_r_rank_b(DM_JOB) { DM_J; dm_r_rank_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_r_fill(DM M) { dm_r_fill_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_r_fill_b(DM_JOB) { DM_J; dm_r_fill_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_r_append(DM M) { dm_r_append_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_r_append_b(DM_JOB) { DM_J; dm_r_append_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_a_done(DM M, int n_host, const int* dn) { dm_a_done_body(M, n_host, dn); }
+__global__ __launch_bounds__(kPar) void k_dm_a_done_b(DM_JOB) { DM_J; dm_a_done_body(M, 0, M.prm_n); }
+__global__ __launch_bounds__(64) void k_dm_touched(DM M) { dm_touched_body(M); }
+__global__ __launch_bounds__(64) void k_dm_touched_b(DM_JOB) { DM_J; dm_touched_body(M); }
+__global__ __launch_bounds__(kOrch) void k_dm_finish(DM M) { dm_finish_body(M); }
+__global__ __launch_bounds__(kOrch) void k_dm_finish_b(DM_JOB) { DM_J; dm_finish_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_table(DM M) { dm_table_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_table_b(DM_JOB) { DM_J; dm_table_body(M); }
+__global__ void k_dm_table_check(DM M) { dm_table_check_body(M); }
+__global__ void k_dm_table_check_b(DM_JOB) { DM_J; dm_table_check_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_rebuild_clear(DM M) { dm_rebuild_clear_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_rebuild_clear_b(DM_JOB) { DM_J; dm_rebuild_clear_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_rebuild_fill(DM M) { dm_rebuild_fill_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_rebuild_fill_b(DM_JOB) { DM_J; dm_rebuild_fill_body(M); }
+// the correction (ApplyTransformAndRehash + RecomputeAllSurfels); a batch job's pose: its DmParams' v[4..15]
+__global__ __launch_bounds__(kPar) void k_dm_at_keys(DM M, DmPose T, float* tc, uint64_t* tk) { dm_at_keys_body(M, T.v, tc, tk); }
+__global__ __launch_bounds__(kPar) void k_dm_at_keys_b(DM_JOB) { DM_J; dm_at_keys_body(M, prm[blockIdx.y].P.v + 4, J.at_c, J.at_k); }
+__global__ __launch_bounds__(kOrch) void k_dm_at_rebuild(DM M, const float* tc, const uint64_t* tk, uint64_t* nk0, float* nc0, int* nn0) { dm_at_rebuild_body(M, tc, tk, nk0, nc0, nn0); }
+__global__ __launch_bounds__(kOrch) void k_dm_at_rebuild_b(DM_JOB) { DM_J; dm_at_rebuild_body(M, J.at_c, J.at_k, J.at_nk, J.at_nc, J.at_nn); }
+__global__ __launch_bounds__(kPar) void k_dm_recompute(DM M) { dm_recompute_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_recompute_b(DM_JOB) { DM_J; dm_recompute_body(M); }
+__global__ __launch_bounds__(kPar) void k_dm_flag(DM M, int flags) { dm_flag_body(M, flags); }
+__global__ __launch_bounds__(kPar) void k_dm_flag_b(DM_JOB, int flags) { DM_J; dm_flag_body(M, flags); }
+// the error bits of all maps of a batch, gathered for one copy (lo_batch_maps_status)
+__global__ __launch_bounds__(kPar) void k_dm_status_b(const DMJob* __restrict__ jobs, int count, int* __restrict__ out) {
+    const int j = blockIdx.x * kPar + threadIdx.x;
+    if (j < count) out[j] = jobs[j].M.cnt ? jobs[j].M.cnt[C_ERR] : 0;      // (a job without a map: cleared entry)
+}
+#undef DM_J
+#undef DM_JOB
 
 }  // namespace dm
 }  // namespace lo
@@ -1593,8 +1620,8 @@ int lo_devmap_apply_transform(lo_devmap* m, const float T[12]) {
     std::memcpy(P.v, T, sizeof(P.v));
     const int G0 = (M.C0 + kPar - 1) / kPar;
     hipLaunchKernelGGL(k_dm_at_keys, dim3(G0), dim3(kPar), 0, m->stream, M, P, m->at_c, m->at_k);
-    hipLaunchKernelGGL(k_dm_at_rebuild, dim3(1), dim3(kOrch), 0, m->stream, M, m->at_c, m->at_k, M.pslot, M.tpfirst,
-                       M.tpcnt, M.tpoff, M.tpfill, M.glist, M.D, m->at_nk, m->at_nc, m->at_nn);
+    hipLaunchKernelGGL(k_dm_at_rebuild, dim3(1), dim3(kOrch), 0, m->stream, M, m->at_c, m->at_k, m->at_nk, m->at_nc,
+                       m->at_nn);
     hipLaunchKernelGGL(k_dm_flag, dim3(1), dim3(64), 0, m->stream, M, static_cast<int>(R_I0 | R_I1 | R_TAB));
     hipLaunchKernelGGL(k_dm_rebuild_clear, dim3(1024), dim3(kPar), 0, m->stream, M);
     hipLaunchKernelGGL(k_dm_rebuild_fill, dim3(1024), dim3(kPar), 0, m->stream, M);
@@ -1730,6 +1757,7 @@ size_t lo_devmap_get_l1(lo_devmap* m, int32_t* keys, uint8_t* has_surfel, float*
 // all active jobs on the batch stream.  The batch keeps a device array of the jobs' descriptors (map, scan, point
 // buffer); entry j goes up again only when it changed -- another map, a moved or replaced table (dm_bind_table), other
 // scan buffers.  What changes per update (DmParams and the active list) goes up in one copy.
+// lo_batch_apply_transform: the correction's nine launches in the same way, on the same descriptors (bm_apply).
 namespace {
 
 struct BatchMaps {
@@ -1795,7 +1823,9 @@ int bm_state(lo_batch* b, const BatchView& V, BatchMaps** out, BatchErr* e) {
 // buffers matter.  A replaced table is emptied (or freed and allocated anew) and refilled on the context stream: the
 // host first waits for the batch's last update (which may still patch the table and write the map), and the batch
 // stream then waits for the refill.  *uploaded is set when the entry went up (the caller records ev_prm behind the copies).
-int bm_refresh(const BatchView& V, BatchMaps* S, lo_devmap* m, int j, bool bind, bool* uploaded, BatchErr* e) {
+// with_scan = false (the correction, which reads no scan): the table is bound and the entry's scan stays what it was.
+int bm_refresh(const BatchView& V, BatchMaps* S, lo_devmap* m, int j, bool bind, bool* uploaded, BatchErr* e,
+               bool with_scan = true) {
     hipStream_t bs = static_cast<hipStream_t>(V.stream);
     DMJob& H = S->h_jobs[j];
     if (!m) {
@@ -1821,8 +1851,10 @@ int bm_refresh(const BatchView& V, BatchMaps* S, lo_devmap* m, int j, bool bind,
             LO_HIP(e, hipEventRecord(S->ev_tab, m->stream));
             LO_HIP(e, hipStreamWaitEvent(bs, S->ev_tab, 0));
         }
-        rc = ctx_filtered_device(m->ctx, &scan, &scan_n);
-        if (rc != LO_OK) { e->err = lo_last_error(m->ctx); return rc; }
+        if (with_scan) {
+            rc = ctx_filtered_device(m->ctx, &scan, &scan_n);
+            if (rc != LO_OK) { e->err = lo_last_error(m->ctx); return rc; }
+        }
     }
     if (S->uid[j] == m->uid && H.M.tab == m->M.tab && H.M.tabl == m->M.tabl && H.scan == scan && H.scan_n == scan_n)
         return LO_OK;
@@ -1830,6 +1862,11 @@ int bm_refresh(const BatchView& V, BatchMaps* S, lo_devmap* m, int j, bool bind,
     H.scan = scan;
     H.scan_n = scan_n;
     H.d_in = m->d_in;
+    H.at_c = m->at_c;
+    H.at_k = m->at_k;
+    H.at_nk = m->at_nk;
+    H.at_nc = m->at_nc;
+    H.at_nn = m->at_nn;
     S->uid[j] = m->uid;
     *uploaded = true;
     LO_HIP(e, hipMemcpyAsync(S->d_jobs + j, &H, sizeof(DMJob), hipMemcpyHostToDevice, bs));
@@ -1932,6 +1969,66 @@ int bm_update(lo_batch* b, const BatchView& V, lo_devmap* const* maps, const uns
     return LO_OK;
 }
 
+// ApplyTransformAndRehash + RecomputeAllSurfels for the active jobs: lo_devmap_apply_transform's nine launches, each
+// for all of them (blockIdx.y = active slot; k_dm_at_rebuild_b: one workgroup per job, side by side)
+int bm_apply(lo_batch* b, const BatchView& V, lo_devmap* const* maps, const unsigned char* active, const float* T,
+             BatchErr* e) {
+    if (V.pending) { e->err = "batch in flight: call lo_batch_result first"; return LO_ERR_STATE; }
+    int rc = bm_check_maps(V, maps, active, e);
+    if (rc != LO_OK) return rc;
+    LO_HIP(e, hipSetDevice(V.device));
+    BatchMaps* S = nullptr;
+    if ((rc = bm_state(b, V, &S, e)) != LO_OK) return rc;
+    hipStream_t bs = static_cast<hipStream_t>(V.stream);
+    int nact = 0;
+    bool up = false;
+    size_t c0_max = 1, c1_max = 1, slots_max = 1;
+    for (int j = 0; j < V.count; ++j) {
+        if (!active[j]) continue;
+        lo_devmap* m = maps[j];
+        if ((rc = bm_refresh(V, S, m, j, true, &up, e, false)) != LO_OK) {
+            if (up && hipEventRecord(S->ev_prm, bs) == hipSuccess) S->prm_pending = true;
+            return rc;
+        }
+        DmJobPrm& Q = S->h_prm[nact++];
+        Q = DmJobPrm{};
+        std::memcpy(Q.P.v + 4, T + 12 * j, 12 * sizeof(float));
+        Q.job = j;
+        const DM& M = m->M;
+        c0_max = std::max(c0_max, static_cast<size_t>(M.C0));
+        c1_max = std::max(c1_max, static_cast<size_t>(M.C1));
+        slots_max = std::max({slots_max, size_t(1) << M.h0l, size_t(1) << M.h1l, size_t(1) << M.tabl});
+    }
+    if (nact == 0) return LO_OK;
+    LO_HIP(e, hipMemcpyAsync(S->d_prm, S->h_prm, sizeof(DmJobPrm) * nact, hipMemcpyHostToDevice, bs));
+    LO_HIP(e, hipEventRecord(S->ev_prm, bs));
+    S->prm_pending = true;
+    // grid.x: what the largest active job's capacity asks for, capped (the bodies stride over what is left) and held
+    // to 65536 workgroups per launch over all jobs, as the update's table passes are
+    const unsigned ny = static_cast<unsigned>(nact);
+    auto blocks = [ny](size_t items, int per) {
+        const size_t want = std::min<size_t>(1024, (items + per - 1) / per);
+        return static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>(want, std::max(1u, 65536u / ny))));
+    };
+    const dim3 g0(blocks(c0_max, kPar), ny), g1(blocks(c1_max, kPar), ny), rgrid(blocks(slots_max, 4 * kPar), ny);
+    const dim3 one(1, ny), par(kPar), orch(kOrch);
+    const DMJob* J = S->d_jobs;
+    const DmJobPrm* Q = S->d_prm;
+    hipLaunchKernelGGL(k_dm_at_keys_b, g0, par, 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_at_rebuild_b, one, orch, 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_flag_b, one, dim3(64), 0, bs, J, Q, static_cast<int>(R_I0 | R_I1 | R_TAB));
+    hipLaunchKernelGGL(k_dm_rebuild_clear_b, rgrid, par, 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_rebuild_fill_b, rgrid, par, 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_recompute_b, g1, par, 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_flag_b, one, dim3(64), 0, bs, J, Q, static_cast<int>(R_TAB));
+    hipLaunchKernelGGL(k_dm_rebuild_clear_b, rgrid, par, 0, bs, J, Q);
+    hipLaunchKernelGGL(k_dm_rebuild_fill_b, rgrid, par, 0, bs, J, Q);
+    LO_HIP(e, hipGetLastError());
+    LO_HIP(e, hipEventRecord(S->ev_done, bs));
+    S->done_recorded = true;
+    return LO_OK;
+}
+
 int bm_status(lo_batch* b, const BatchView& V, lo_devmap* const* maps, int* out, BatchErr* e) {
     int rc = bm_check_maps(V, maps, nullptr, e);
     if (rc != LO_OK) return rc;
@@ -2003,6 +2100,15 @@ int lo_batch_update_maps(lo_batch* b, lo_devmap* const* maps, const unsigned cha
     if (!maps || !active || !T) { batch_set_error(b, "null argument"); return LO_ERR_ARG; }
     BatchErr e;
     const int rc = bm_update(b, batch_view(b), maps, active, T, max_distance, &e);
+    if (rc != LO_OK) batch_set_error(b, e.err.c_str());
+    return rc;
+}
+
+int lo_batch_apply_transform(lo_batch* b, lo_devmap* const* maps, const unsigned char* active, const float* T) {
+    if (!b) return LO_ERR_ARG;
+    if (!maps || !active || !T) { batch_set_error(b, "null argument"); return LO_ERR_ARG; }
+    BatchErr e;
+    const int rc = bm_apply(b, batch_view(b), maps, active, T, &e);
     if (rc != LO_OK) batch_set_error(b, e.err.c_str());
     return rc;
 }

@@ -641,6 +641,22 @@ class BatchOptimizer:
                                                act.ctypes.data_as(C.POINTER(C.c_uint8)), _fptr(T),
                                                float(max_distance)))
 
+    def apply_transform(self, maps, active, transforms):
+        """The map correction after accepted loops for all active jobs in one set of launches
+        (lo_batch_apply_transform): for each job j with ``active[j]``, what
+        ``lo_devmap_apply_transform(maps[j], transforms[j])`` does -- ApplyTransformAndRehash and RecomputeAllSurfels
+        on the job's ``DeviceVoxelMap``.  An inactive job's transform is not read.  Enqueues on the batch stream and
+        returns; ``maps_status`` waits.  In a KDTree batch follow it with ``sync_points`` on the same ``active``."""
+        B = len(self.optimizers)
+        act = np.ascontiguousarray(np.asarray(active).astype(bool).astype(np.uint8))
+        if act.shape != (B,):
+            raise ValueError(f"need {B} active flags")
+        T = np.ascontiguousarray(np.stack([_as_pose(t) for t in transforms]), dtype=np.float32)
+        if T.shape != (B, 12):
+            raise ValueError(f"need {B} transforms")
+        self._check(lib().lo_batch_apply_transform(self._b, self._map_handles(maps),
+                                                   act.ctypes.data_as(C.POINTER(C.c_uint8)), _fptr(T)))
+
     def sync_points(self, maps, active=None):
         """RebuildKdTree for a KDTree batch's keyframes (lo_batch_sync_points): for each job j with ``active[j]``
         (default: every job), what ``lo_devmap_sync_points(maps[j])`` does -- optimizer j's correspondence grid rebuilt
