@@ -205,7 +205,8 @@ int lo_set_pipeline(lo_ctx* ctx, int enable, int main_iterations);
  *    call lo_icp_flush first, or switch the overlap off.
  * NOTE lo_stream: it is a getter that may launch the pending hold (whoever asks for the stream is about to enqueue on
  * it; the device map, the loop detector and the map builder take it this way); poll the handle once, not in a loop.
- * lo_scan_overlap_status: out[0] enabled, out[1] scans whose head was enqueued in front of the previous scan's hold.
+ * lo_scan_overlap_status: out[0] enabled, out[1] queued scans that did not wait for the scan before them: scans whose
+ * head was enqueued in front of the previous scan's hold, and scans launched in a lockstep group (SCAN GROUPS below).
  * TWO SCANS IN FLIGHT (lo_set_scan_depth; LO_OVERLAP_DEPTH=1 in the environment, or depth 1 here, gives the
  * one pending hold described above, launch for launch).  With depth 2 a queued scan k enqueues the hold of scan k - 2
  * -- the scan that last used its set of per-scan state -- in front of its own head, and no longer the hold of scan
@@ -235,6 +236,41 @@ int lo_set_scan_overlap(lo_ctx* ctx, int enable);
 int lo_scan_overlap_status(lo_ctx* ctx, long long out[2]);
 int lo_set_scan_depth(lo_ctx* ctx, int depth);
 int lo_set_scan_lanes(lo_ctx* ctx, int lanes);
+/* SCAN GROUPS (default on; lo_set_scan_group, LO_SCAN_GROUP in the environment).  A caller that queues scans back to
+ * back on one context hands the library a batch one scan at a time, and the queue runs it as one: a queued scan that
+ * the ring above would overlap -- a small surfel scan with PKO, caller-owned points, nothing timed; in reference-exact
+ * mode at most 8192 points -- is not launched when it is enqueued but appended to the open GROUP, and the group's scans
+ * advance through their Gauss-Newton iterations in lockstep, one launch per kernel per iteration for all of them (the
+ * launch list of lo_batch_optimize_async), on one of two group streams.  Each scan has its own set of per-scan state
+ * (made when first used, ~1.4 MB at the default max_points), and its result -- pose, statistics, iteration logs, its
+ * lo_icp_queue_records record -- is bit-identical to a solo run.
+ * The open group is launched when it holds `group` scans; at every call that enqueues the ring's pending holds
+ * (lo_icp_flush, lo_icp_result, lo_sync, lo_icp_export_pose, lo_icp_queue_records, lo_stream, every setter, every map
+ * or table change, lo_batch_* over this context, any scan that is not groupable), after which the context stream also
+ * waits for the groups; and at once when a scan is enqueued while nothing of the context is in flight, so a lone
+ * asynchronous scan starts as it always did (down the ring).
+ * group: 0 selects the default (32), 1 switches grouping off (every queued scan takes the ring), 2 .. 32 scans per
+ * group; LO_ERR_ARG otherwise.  An explicit choice of the ring keeps the ring: pipeline or scan overlap off, a split
+ * chosen with lo_set_pipeline(.., main_iterations >= 1) or LO_PIPE_MAIN, a depth chosen with lo_set_scan_depth /
+ * lo_set_scan_lanes / LO_OVERLAP_DEPTH.  So does a context that is not alone in the process in having queued scans in
+ * flight (one scan in flight each, above).
+ * CHANGED CONTRACT (default on):
+ *  - the device buffers of queued scans must stay valid and unchanged until their result or record has been read or
+ *    lo_sync has returned: that is now up to 2 x group scans back (64 by default), where it was four;
+ *  - a scan queued behind a running one may not START until its group fills or the context is next touched;
+ *    lo_icp_flush starts it (and, as before, orders the context stream behind it).  "Running" is what the host can
+ *    tell without a device round trip: a group that has not reported done, or a ring scan whose hold is still pending
+ *    -- i.e. ANY earlier queued scan whose result was not read and after which no call was made on the context, even
+ *    if the device finished it long ago.  A second lone asynchronous scan behind such a scan therefore waits in the
+ *    open group; a caller that polls its own stream for it must call lo_icp_flush first.
+ * ORDER AND MEMORY: a group runs behind everything enqueued on the context stream before it left (one event per group),
+ * so asynchronous map changes made through the library and work the caller enqueued on a shared stream are seen by the
+ * scans queued after them.  At the default, a context that queues long runs allocates up to 64 sets of per-scan state
+ * (2 x 32, ~1.4 MB each at the default max_points: ~90 MB), each made the first time a group grows to that size.
+ * lo_scan_group_status: out[0] scans per group in effect, out[1] lockstep groups launched, out[2] scans they carried,
+ * out[3] scans waiting in the open group (enqueued, not yet launched).  Reads the counters only: it launches nothing. */
+int lo_set_scan_group(lo_ctx* ctx, int group);
+int lo_scan_group_status(lo_ctx* ctx, long long out[4]);
 /* Enqueue the pending holds of the last queued scans (at most the depth in use) on the context stream now, oldest first (no-op when
  * there is none): what follows on that stream sees those scans' final results.  Does not wait on the host. */
 int lo_icp_flush(lo_ctx* ctx);

@@ -15,6 +15,7 @@
 // planes, residuals, ballots and block statistics they write are what the surfel launch writes, so everything after
 // them is the same launch sequence.
 #include "lo_ctx_def.h"
+#include "lo_lockstep.h"
 
 #include <climits>
 
@@ -27,10 +28,6 @@ static constexpr int kBatchOneWaveMin = 0x7fffffff;
 // the fused form's fp64 solve holds the 8-wave accumulate at 128 VGPRs (2 workgroups per CU; split: 70, 3 per CU).
 // Measured: 4096 jobs 1.037M -> 1.090M scans/s, 1024 857k -> 875k; at 64-256 jobs the extra launch costs ~1 %.
 static constexpr int kBatchSplitSolveMin = 1024;
-// KDTree batches, the unresolved pass (k_knn_brute_b): at most this many 1024-thread workgroups over all jobs (two per
-// CU), and at most kBatchBrutePerJob of them on one job (what a single context's k_knn_brute launch gets)
-static constexpr int kBatchBruteWGs = 512;
-static constexpr int kBatchBrutePerJob = 64;
 
 struct lo_batch {
     std::vector<lo_ctx*> ctx;
@@ -133,15 +130,7 @@ static int batch_alloc(lo_batch* b) {
     LO_HIP(b, hipEventCreate(&b->evf0));
     LO_HIP(b, hipEventCreate(&b->evf1));
     b->nf.assign(B, 0);
-    LO_HIP(b, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pko_tb<4, false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kMaxBlocks * sizeof(int))));
-    LO_HIP(b, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pko_tb<1, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kMaxBlocks * sizeof(int))));
-    LO_HIP(b, hipFuncSetAttribute(reinterpret_cast<const void*>(k_exact_acc_b), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  static_cast<int>(kXcLdsBytes)));
-    // reference-exact jobs' iteration-0 scale (k_exact_scale_cb, up to 80 KB of dynamic LDS): a process that only
-    // batches must not depend on a single-context exact optimize having set the attribute first
-    LO_HIP(b, exact_scale_c_prepare());
+    LO_HIP(b, lockstep_prepare());                     // the lockstep kernels' dynamic-LDS attributes
     // KDTree batches: k_knn_b, k_knn_brute_b and k_plane_b use static LDS only (no attribute to set); a job that runs
     // on its own context (a large exact job, an all-pairs grid, a re-run after a tie) goes through enqueue_optimize,
     // whose kernels' attributes lo_create set for a KDTree context (kd_alloc)
@@ -210,21 +199,6 @@ static int batch_filter(lo_batch* b, const float* const* raw, const size_t* n_ra
     return LO_OK;
 }
 
-// The correspondence stage of one lockstep iteration for the first nact jobs of d_P: the surfel lookup, or (KDTree
-// batch) the grid search, the unresolved queries and the plane fit, each one launch for all jobs.  max_nb / max_knn:
-// the largest job's k_correspond / k_knn grid.
-static void launch_correspond_batch(lo_batch* b, int nact, int max_nb, int max_knn, int with_stats, int init) {
-    const dim3 blk(kBlock);
-    if (!b->kd) {
-        hipLaunchKernelGGL(k_correspond_b, dim3(max_nb, nact), blk, 0, b->stream, b->d_P, with_stats, init);
-        return;
-    }
-    const int per = std::max(1, std::min(kBatchBrutePerJob, kBatchBruteWGs / nact));
-    const int wgs = static_cast<int>(std::min<long long>(kBatchBruteWGs, static_cast<long long>(nact) * per));
-    hipLaunchKernelGGL(k_knn_b, dim3(max_knn, nact), blk, 0, b->stream, b->d_P, init);
-    hipLaunchKernelGGL(k_knn_brute_b, dim3(wgs), dim3(1024), 0, b->stream, b->d_P, nact, per);
-    hipLaunchKernelGGL(k_plane_b, dim3(max_nb, nact), blk, 0, b->stream, b->d_P, with_stats);
-}
 static int knn_blocks(int n) { return static_cast<int>((static_cast<long long>(n) * kKnnGroup + kBlock - 1) / kBlock); }
 
 extern "C" {
@@ -402,34 +376,18 @@ int lo_batch_optimize_async(lo_batch* b, const float* const* d_pts, const size_t
         }
     }
     if (nact > 0) {
-        const int pko_wgs = std::max(1, std::min(b->pko_max, b->pko_budget / nact));
-        const size_t pre_bytes = static_cast<size_t>(max_nb) * sizeof(int);
-        const dim3 blk(kBlock);
-        for (int it = 0; it < b->max_iters; ++it) {
-            launch_correspond_batch(b, nact, max_nb, max_knn, it == 0 ? 1 : 0, it == 0 ? 1 : 0);
-            if (it == 0 && nexl > 0) {
-                launch_exact_scale_cb(b->d_P + nfast, nexl, n_max_ex, b->stream);
-                LO_HIP(b, hipGetLastError());                 // e.g. a dynamic-LDS launch the attribute did not allow
-            }
-            if (nact >= b->one_wave_min)
-                hipLaunchKernelGGL((k_pko_tb<1, true>), dim3(1, nact), dim3(64), pre_bytes, b->stream, b->d_P, it);
-            else
-                hipLaunchKernelGGL((k_pko_tb<4, false>), dim3(pko_wgs, nact), dim3(256), pre_bytes, b->stream, b->d_P, it);
-            if (nexl > 0)
-                hipLaunchKernelGGL(k_exact_acc_b, dim3(nexl), dim3(256), kXcLdsBytes, b->stream, b->d_P + nfast, it);
-            if (nfast == 0) continue;
-            if (max_acc <= kFuseMaxBlocks) {           // small jobs: one 8-wave workgroup accumulates + solves
-                if (nfast < b->split_solve_min) {
-                    hipLaunchKernelGGL(k_accumulate_b1<true>, dim3(1, nfast), dim3(512), 0, b->stream, b->d_P, it);
-                } else {
-                    hipLaunchKernelGGL(k_accumulate_b1<false>, dim3(1, nfast), dim3(512), 0, b->stream, b->d_P, it);
-                    hipLaunchKernelGGL(k_solve_b1, dim3(nfast), dim3(kBlock), 0, b->stream, b->d_P, it);
-                }
-            } else {
-                hipLaunchKernelGGL(k_accumulate_b, dim3(max_acc, nfast), blk, 0, b->stream, b->d_P, it);
-                hipLaunchKernelGGL(k_solve_b, dim3(nfast), dim3(kSolveThreads), 0, b->stream, b->d_P, it);
-            }
-        }
+        LockstepShape sh;
+        sh.nfast = nfast;
+        sh.nexl = nexl;
+        sh.max_nb = max_nb;
+        sh.max_knn = max_knn;
+        sh.max_acc = max_acc;
+        sh.n_max_ex = n_max_ex;
+        sh.kd = b->kd;
+        sh.pko_wgs = std::max(1, std::min(b->pko_max, b->pko_budget / nact));
+        sh.one_wave = nact >= b->one_wave_min;
+        sh.split_solve = nfast >= b->split_solve_min;
+        LO_HIP(b, launch_lockstep(b->stream, b->d_P, sh, b->max_iters));
     }
     if (ntot > 0) {
         hipLaunchKernelGGL(k_export_batch, dim3(ntot), dim3(64), 0, b->stream, b->d_P, b->d_rec);
@@ -504,9 +462,14 @@ int lo_batch_bench_correspond(lo_batch* b, int reps, float* avg_ms) {
     }
     // every job back at its initial pose with a fresh GN state (init launch), then reps plain launches (a KDTree
     // batch: the stage's three launches each time)
-    launch_correspond_batch(b, nact, max_nb, max_knn, 1, 1);
+    LockstepShape sh;
+    sh.nexl = nact;                                     // (the correspondence stage does not tell the classes apart)
+    sh.max_nb = max_nb;
+    sh.max_knn = max_knn;
+    sh.kd = b->kd;
+    launch_lockstep_correspond(b->stream, b->d_P, sh, 1, 1);
     LO_HIP(b, hipEventRecord(b->ev0, b->stream));
-    for (int r = 0; r < reps; ++r) launch_correspond_batch(b, nact, max_nb, max_knn, 0, 0);
+    for (int r = 0; r < reps; ++r) launch_lockstep_correspond(b->stream, b->d_P, sh, 0, 0);
     LO_HIP(b, hipEventRecord(b->ev1, b->stream));
     LO_HIP(b, hipGetLastError());
     LO_HIP(b, hipEventSynchronize(b->ev1));

@@ -14,6 +14,7 @@ hipError_t sync_all(lo_ctx* c) {
     hipError_t e = c->stream ? hipStreamSynchronize(c->stream) : hipSuccess;
     for (hipStream_t s : c->q.s_tail)
         if (e == hipSuccess && s) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = group_sync(c);              // (the context stream already waits for them: flush_hold)
     return e;
 }
 }  // namespace lo
@@ -231,6 +232,7 @@ void lo_destroy(lo_ctx* c) {
     (void)sync_all(c);
     for (hipStream_t s : c->q.s_tail)
         if (s) (void)hipStreamDestroy(s);
+    group_release(c);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (hipEvent_t e : c->st_ev) (void)hipEventDestroy(e);

@@ -190,11 +190,20 @@ void launch_correspond(lo_ctx* c, const KParams& P, int with_stats, bool kd);
 void launch_correspond_first(lo_ctx* c, const KParams& P0, bool kd, int with_stats = 1);
 void launch_exact_scale_any(lo_ctx* c, const KParams& P, int n2, hipStream_t s);
 int enqueue_optimize(lo_ctx* c, const float* d_pts, size_t n, const float T_init[12], const int* n_dev = nullptr);
+int enqueue_ring(lo_ctx* c, const float* d_pts, size_t n, const float T_init[12], const int* n_dev);
 int loop_rerun_with_order(lo_ctx* c, const float* d_curr, size_t n_curr, const float T_curr[12], size_t n_matched,
                           const float T_matched[12], float T_rel_out[12], float* inlier_ratio, lo_iter_log* logs,
                           lo_stats* st);
 // lo_scanq.hip
-inline ScanLane& cur(lo_ctx* c) { return c->q.lanes[c->q.lane]; }   // the lane of the last enqueued scan
+// the per-scan state of the last enqueued scan: its lane's, or (a grouped scan) its set in the group's slot
+inline ScanLane& cur(lo_ctx* c) { return c->q.grp.cur ? *c->q.grp.cur : c->q.lanes[c->q.lane]; }
+// ... back on the ring's current lane: whatever builds KParams for a launch of its own (a ring scan, a batch job, the
+// loop-closure solve, the parity entry points) does so on a lane, which has the candidate buffers
+inline void leave_group_set(lo_ctx* c) {
+    if (!c->q.grp.cur) return;
+    c->q.grp.cur = c->q.grp.prev = nullptr;
+    ++c->cfg_gen;
+}
 int lane_alloc_base(lo_ctx* c, ScanLane& L);    // everything but the candidate buffers, sized by max_points
 int lane_alloc_cand(lo_ctx* c, ScanLane& L);    // the candidate buffers, sized by the alpha grid (d_acc_part last)
 int flush_hold(lo_ctx* c);     // the pending holds of the last pipelined scans, enqueued on the context stream now
@@ -202,6 +211,14 @@ int pipe_recover(lo_ctx* c);
 ScanPlanIn scan_snapshot(const lo_ctx* c, bool cand, bool timed, bool dev_count);
 int apply_plan(lo_ctx* c, const ScanPlan& plan);
 int emit_pipelined(lo_ctx* c, const ScanPlan& plan, KParams& P, KParams& P0, int n2, unsigned ring_run);
+// scan groups (lo_scan_group_plan.h)
+GroupPlanIn group_snapshot(const lo_ctx* c, size_t n, bool cand, bool timed, bool dev_count);
+int group_append(lo_ctx* c, const GroupPlan& plan, const float* d_pts, size_t n, const float T_init[12]);
+int group_emit(lo_ctx* c);     // the open group leaves (lockstep on its slot's stream, or scan by scan down the ring)
+int group_flush(lo_ctx* c);    // ... and the context stream waits for every slot's last group (flush_hold calls this)
+int group_join(lo_ctx* c);     // the context stream behind every slot's last group (flush_hold, every ring-path scan)
+hipError_t group_sync(lo_ctx* c);
+void group_release(lo_ctx* c);
 
 // ---- per-scan helpers on the launch path of every optimize, single and batched: inline, as when one file held them
 // PKO workgroups: one alpha of the JS grid per workgroup (each fits the GMM redundantly), capped at kPkoMaxWGs
@@ -215,6 +232,7 @@ inline int pko_grid(const lo_ctx* c) {
 constexpr size_t kPkoSoloBytes = 64 * 1024;   // + the ~22-27 KB static part: more than half of a CU's 160 KB
 // the speculative normal equations and candidate records (first PKO optimize, and after lo_update_config dropped them)
 inline int ensure_acc_part(lo_ctx* c) {
+    leave_group_set(c);
     ScanLane& L = cur(c);
     if (L.d_acc_part || !c->cfg.use_adaptive_m_estimator) return LO_OK;    // (set last: "all three")
     const int rc = lane_alloc_cand(c, L);

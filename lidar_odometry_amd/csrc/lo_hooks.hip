@@ -465,12 +465,15 @@ int lo_debug_other_lane_record(lo_ctx* c, float out16[16]) {
     if (!c || !out16) return LO_ERR_ARG;
     LO_HIP(c, hipSetDevice(c->device));
     LO_HIP(c, sync_all(c));
-    if (c->q.prev_lane < 0 || !c->q.lanes[c->q.prev_lane].d_st) {
+    // (two grouped scans: the one before the last has its own set of per-scan state in the group's slot)
+    const ScanLane* other = (c->q.grp.cur && c->q.grp.prev) ? c->q.grp.prev
+                            : c->q.prev_lane >= 0 ? &c->q.lanes[c->q.prev_lane] : nullptr;
+    if (!other || !other->d_st) {
         c->err = "lo_debug_other_lane_record: no scan has overlapped yet";
         return LO_ERR_STATE;
     }
     std::vector<char> h(offsetof(DevState, logs));
-    LO_HIP(c, hipMemcpy(h.data(), c->q.lanes[c->q.prev_lane].d_st.get(), h.size(), hipMemcpyDeviceToHost));
+    LO_HIP(c, hipMemcpy(h.data(), other->d_st.get(), h.size(), hipMemcpyDeviceToHost));
     const DevState* st = reinterpret_cast<const DevState*>(h.data());   // (header fields only)
     for (int k = 0; k < 12; ++k) out16[k] = st->pose[k];
     out16[12] = static_cast<float>(st->status);

@@ -531,5 +531,27 @@ __global__ void k_export_batch(const KParams* __restrict__ PB, lo_batch_rec* out
     if (t == 18) R.pad = st->kd_tie ? 1.0f : 0.0f;
 }
 
+// Scan groups (lo_scan_group_plan.h): every job's 16-float record (k_export_pose's layout) into its slot of the
+// context's record ring (KParams::rec, handed out in enqueue order), then the group's number into the slot's completion
+// word in host memory -- the host reads it to tell whether anything of the context is still in flight, never to order a
+// read: results are read behind the slot's stream (flush_hold).  One workgroup; njobs <= kMaxGroup.
+__global__ void k_export_group(const KParams* __restrict__ PB, int njobs, uint32_t* hdone, uint32_t seq) {
+    for (int i = threadIdx.x; i < njobs * 16; i += blockDim.x) {
+        const int j = i >> 4, t = i & 15;
+        const DevState* st = PB[j].st;
+        float* rec = PB[j].rec;
+        if (!rec) continue;
+        float v = 0.0f;
+        if (t < 12) v = st->pose[t];
+        else if (t == 12) v = static_cast<float>(st->status);
+        else if (t == 13) v = static_cast<float>(st->iter);
+        else if (t == 14) v = static_cast<float>(st->n_corr);
+        rec[t] = v;
+    }
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_store(hdone, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 }  // namespace lo
 

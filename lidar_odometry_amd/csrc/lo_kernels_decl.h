@@ -48,6 +48,7 @@ __global__ void k_solve_b1(const KParams* PB, int it);
 __global__ void k_solve_b(const KParams* PB, int it);
 __global__ void k_export_batch(const KParams* PB, lo_batch_rec* out);
 __global__ void k_exact_acc_b(const KParams* PB, int it);
+__global__ void k_export_group(const KParams* PB, int njobs, uint32_t* hdone, uint32_t seq);
 void launch_exact_scale_cb(const KParams* PB, int njobs, int n_max, hipStream_t s);
 struct MapPatchRec;
 __global__ void k_map_patch(Slot* tab, uint32_t log2cap, const MapPatchRec* rec, int n);

@@ -254,11 +254,32 @@ static void emit_single(lo_ctx* c, const KParams& P, const KParams& P0, int n2, 
 // One scan: snapshot of the queue, plan (lo_scan_plan.h), the plan's flush / lane switch / holds, the scan's KParams,
 // then its launches -- down the scan pipeline (emit_pipelined) or on the context stream alone.
 int enqueue_optimize(lo_ctx* c, const float* d_pts, size_t n, const float T_init[12], const int* n_dev) {
-    const lo_config& g = c->cfg;
     std::memcpy(c->T_init, T_init, sizeof(float) * 12);
     c->last_n = n;
     c->last_pts = d_pts;
     c->last_ndev = n_dev;
+    // Scan groups (lo_scan_group_plan.h): a groupable scan joins the open group and is launched with it; anything else
+    // sends the open group out first (record order) and takes the ring path.  A scan that would leave at once as a
+    // group of one (nothing of the context in flight) goes straight down the ring, as it always did.
+    const GroupPlan gp = plan_group(group_snapshot(c, n, cand_scan(c, n), c->sync_call, n_dev != nullptr));
+    if (gp.append && (gp.lockstep || !gp.emit)) {
+        int rc = group_append(c, gp, d_pts, n, T_init);
+        if (rc == LO_OK && gp.emit) rc = group_emit(c);
+        if (rc != LO_OK) return rc;
+        c->last_timed = false;
+        c->pending = true;
+        return LO_OK;
+    }
+    const int rcg = group_emit(c);
+    if (rcg != LO_OK) return rcg;
+    return enqueue_ring(c, d_pts, n, T_init, n_dev);
+}
+
+// The ring path of one scan (and of every scan of a group too small for lockstep, group_emit).
+int enqueue_ring(lo_ctx* c, const float* d_pts, size_t n, const float T_init[12], const int* n_dev) {
+    const lo_config& g = c->cfg;
+    leave_group_set(c);
+    { const int rcj = group_join(c); if (rcj != LO_OK) return rcj; }   // behind the groups still running (record order)
     const unsigned ring_run = c->q.ring_n;                // the run of pipelined scans ends here unless this is one
     c->q.ring_n = 0;
     // HIP events only for synchronous calls (gpu_ms): a marker packet costs ~5-7 us of device time per scan

@@ -5,6 +5,7 @@
 
 #include "lo_buf.h"
 #include "lo_device.h"
+#include "lo_scan_group_plan.h"
 #include "lo_scan_plan.h"
 
 namespace lo {
@@ -25,6 +26,55 @@ struct ScanLane {
     DevBuf<double> d_acc_part;      // speculative normal equations (lane_alloc_cand)
     DevBuf<float> d_cand_rec;       //   and each candidate's solved GN step [NA + 1][kCandWords]
     DevBuf<unsigned> d_cand_cnt;    //   per-candidate workgroup arrivals (zero between launches)
+};
+
+// Scan groups (lo_scan_group_plan.h; lo_set_scan_group / LO_SCAN_GROUP): queued scans that leave as lockstep runs.
+// A slot is one group's worth of everything such a run owns: a stream, up to kMaxGroup sets of per-scan state (made the
+// first time a scan uses them, without the speculative candidate buffers, which a lockstep run never touches), and the
+// pinned staging and device copies of the jobs' KParams and initial poses.
+constexpr int kGroupPkoWGs = 256;   // PKO workgroups per launch over all jobs of a group (>= 1 per job)
+struct GroupJob {                   // one scan of the open group, as it was enqueued
+    const float* pts;
+    int n;
+    float T0[12];
+    bool exact;
+    KParams P;                      // as make_params built it on the scan's own set of per-scan state
+};
+struct GroupSlot {
+    hipStream_t s = nullptr;
+    ScanLane sets[kMaxGroup];
+    int n_sets = 0;                 // sets allocated so far (the first n_sets)
+    PinnedBuf<KParams> h_Ps;        // the jobs' params in lockstep order (fast jobs, then exact ones): what is uploaded
+    DevBuf<KParams> d_P;
+    PinnedBuf<float> h_T0;          // sorted order
+    DevBuf<float> d_T0;
+    hipEvent_t ev_up = nullptr;     // behind the slot's last uploads: the host waits for it before rewriting the staging
+    bool up_pending = false;
+    hipEvent_t ev_done = nullptr;   // behind the slot's last group (flush_hold: the context stream waits for it)
+    bool unjoined = false;          //   the context stream has not yet been made to wait for the slot's last group
+    uint32_t seq = 0;               // groups emitted on this slot; the group's export kernel stores it to h_done[slot]
+};
+struct ScanGroups {
+    int setting = 0;                // lo_set_scan_group: 0 default, 1 off, 2..kMaxGroup
+    bool ready = false;             // streams, events, staging and the completion words exist
+    GroupSlot slot[kGroupSlots];
+    int open_slot = 0;
+    int open_n = 0;                 // scans appended to the open group
+    GroupJob jobs[kMaxGroup];
+    ScanLane* cur = nullptr;        // the per-scan state of the last enqueued scan when that was a grouped one (cur(c))
+    ScanLane* prev = nullptr;       //   and of the grouped scan enqueued before it (lo_debug_other_lane_record)
+    MappedBuf<uint32_t> h_done;     // device-mapped, one word per slot: the last group of the slot that has finished
+    uint32_t* d_hdone = nullptr;    //   its device alias (not owned)
+    hipEvent_t ev_ring = nullptr;   // behind the ring's holds on the context stream, when a group follows ring scans
+    int pko_budget = kGroupPkoWGs;  // PKO workgroups per launch over a group's jobs (LO_SCAN_GROUP_PKO_WGS)
+    bool active = false;            // this context counts among those with queued scans in flight (holds pending, an
+                                    //   open group, or a group the context stream has not been made to wait for)
+    unsigned long long n_groups = 0, n_scans = 0;   // lockstep groups emitted, and scans they carried (lo_scan_group_status)
+    bool in_flight() const {
+        for (int i = 0; i < kGroupSlots; ++i)
+            if (slot[i].seq != 0 && __atomic_load_n(h_done.get() + i, __ATOMIC_ACQUIRE) != slot[i].seq) return true;
+        return false;
+    }
 };
 
 // Scan pipeline (lo_set_pipeline; on by default): GN iterations >= the split of a small PKO scan go to a tail stream,
@@ -85,8 +135,10 @@ struct ScanQueue {
     unsigned long long ring_pos = 0;   // pipelined scans given a slot so far (slot = ring_pos % kRingRecords)
     unsigned ring_n = 0;            // of which the last ring_n were queued with no other scan in between (<= kRingRecords)
     unsigned long long overlapped = 0;   // scans whose head was enqueued in front of the previous scan's hold
+    ScanGroups grp;                 // scan groups (above)
 
-    void from_env();                // LO_PIPE, LO_PIPE_MAIN, LO_OVERLAP, LO_OVERLAP_DEPTH, LO_PIPE_WAIT_MS, LO_PIPE_FAIL_AT
+    void from_env();                // LO_PIPE, LO_PIPE_MAIN, LO_OVERLAP, LO_OVERLAP_DEPTH, LO_PIPE_WAIT_MS, LO_PIPE_FAIL_AT,
+                                    //   LO_SCAN_GROUP
     bool flagged() const { return h_broken && __atomic_load_n(h_broken.get(), __ATOMIC_ACQUIRE) != 0u; }
 };
 }  // namespace lo

@@ -165,6 +165,23 @@ class IterativeClosestPointOptimizer:
         if rc != 0:
             raise RuntimeError(f"lo_set_scan_lanes failed ({rc})")
 
+    def set_scan_group(self, group: int = 0):
+        """Queued scans per lockstep group (lo_set_scan_group): 0 the default, 1 off (every queued scan takes the scan
+        ring), 2 to 32.  The device buffers of the last 2 x group queued scans must stay valid until the result is
+        read, and a scan queued behind a running one starts when its group fills or at the next call on the optimizer.
+        Results are identical for every value."""
+        rc = self._L.lo_set_scan_group(self.ctx, int(group))
+        if rc != 0:
+            raise RuntimeError(f"lo_set_scan_group failed ({rc})")
+
+    def scan_group_status(self):
+        """(scans per group in effect, lockstep groups launched, scans they carried, scans waiting in the open group)."""
+        out = (C.c_longlong * 4)()
+        rc = self._L.lo_scan_group_status(self.ctx, out)
+        if rc != 0:
+            raise RuntimeError(f"lo_scan_group_status failed ({rc})")
+        return int(out[0]), int(out[1]), int(out[2]), int(out[3])
+
     def queue_records(self, n_last: int) -> np.ndarray:
         """The records of the last n_last queued pipelined scans, oldest first (lo_icp_queue_records): an
         (n_last, 16) float32 array of pose[12], status, iterations, n_corr, 0.  Drains the context."""
